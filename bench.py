@@ -18,8 +18,17 @@ contact / TOI load; the timed region must contain finished episodes (asserted).
 Output: ONE JSON line on rank 0 with `roofline` (step kernel, VALU-bound: the algorithmic fp32 FLOPs of the
 workload per launch / measured average kernel duration vs the 157.3 TFLOP/s fp32 vector peak;
 `roofline.hbm`: algorithmic bytes / the same duration vs 8 TB/s; `roofline.valu_issue`: issued active-lane VALU
-operations from the committed SQ counters, reported beside, not as the headline) and `cpu_baseline` (the C
-oracle's batched context on the same workload on host cores, plus the C1 single-env number; rank 0 at N=1 only).
+operations from the committed SQ counters, reported beside, not as the headline).
+
+A plain run does only what the headline needs: set-up, pre-roll, warmup, the --steps timed hk_step launches, the
+line.  --full adds the side legs, each a run of its own after the timed steps: `rollout`, `streams`,
+`facade_single_env`, `c5_round`, `c4_shard` and `cpu_baseline` (the C oracle's batched context on the same
+workload on host cores, plus the C1 single-env number; rank 0 at N=1 only); their options (--rollout, --streams,
+--facade-steps, --c5-steps, --c4-steps, --no-cpu-baseline, --cpu-*) size or switch off single legs of a --full run.
+
+--dump-outputs DIR writes what the last timed hk_step launch handed its caller -- obs [N,18], reward [N], done [N],
+info [N,4] -- as DIR/<name>.npy (float32).  The inputs are the seeded device state, so the same arguments give the
+same arrays from run to run and from build to build.
 """
 import argparse
 import json
@@ -59,6 +68,13 @@ def _args():
     ap.add_argument("--arenas", type=int, default=65536, help="arenas per GPU")
     ap.add_argument("--policy", choices=["basic", "random"], default="basic")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the side legs (rollout, streams, facade_single_env, c5_round, "
+                         "c4_shard, cpu_baseline); without it the options that size those legs have no effect")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's obs / reward / done / info as DIR/<name>.npy (float32; rank r > 0 "
+                         "writes <name>_rank<r>.npy; above 64 MB a fixed seeded sample of arenas, listed in "
+                         "arena_index.npy)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--rollout", type=int, default=50,
                     help="also time hk_rollout with this many steps per launch (0 = skip); reported under 'rollout'")
@@ -432,6 +448,28 @@ class RehearsalEnv:
         pass
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path, rank, out):
+    """--dump-outputs: the arrays the last timed hk_step launch wrote for its caller, as float32 .npy files.  At
+    most 64 MB in all: a larger output is cut to a fixed sample of arenas (default_rng(0), sorted; the same for
+    every run of the same size), whose indices go to arena_index.npy."""
+    import numpy as np
+
+    n = len(out["obs"])
+    row_bytes = sum(4 * int(np.prod(a.shape[1:], dtype=np.int64)) for a in out.values()) + 8
+    if n * row_bytes > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_LIMIT_BYTES // row_bytes, replace=False))
+        out = {k: a[idx] for k, a in out.items()}
+        out["arena_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    tag = f"_rank{rank}" if rank else ""
+    for name, a in out.items():
+        np.save(os.path.join(path, f"{name}{tag}.npy"),
+                np.ascontiguousarray(a, dtype=np.float64 if name == "arena_index" else np.float32))
+
+
 def provenance():
     """Which code the numbers describe: the library's build hash (its .srchash sidecar), the hash of the
     sources in this tree, and whether the committed counter summaries were collected at that same hash."""
@@ -452,6 +490,8 @@ def main():
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if args.arenas <= 0 or args.steps <= 0:
         sys.exit(f"bench.py: rank {rank}: --arenas and --steps must be positive")
+    if args.dump_outputs and args.rehearse:
+        sys.exit("bench.py: --dump-outputs needs the GPU path; --rehearse steps no arenas")
     import torch
     import torch.distributed as dist
 
@@ -523,10 +563,15 @@ def main():
     cnt = env.counters()
     if world > 1:
         elapsed, cnt = reduce_over_ranks(elapsed, cnt, dist)
+    if args.dump_outputs:
+        # the buffers the timed launches wrote (io above), as the last of them left them
+        dump_outputs(args.dump_outputs, rank, {"obs": env.obs_buf.cpu().numpy(), "reward": env.reward_buf.cpu().numpy(),
+                                               "done": env.done_buf.cpu().numpy(), "info": env.info_buf.cpu().numpy()})
     rollout = streams = None
-    if gpu and args.rollout > 1:
+    full = gpu and args.full
+    if full and args.rollout > 1:
         rollout = _time_rollout(env, N, torch, dist, world, dev, args)
-    if gpu and args.streams > 1:
+    if full and args.streams > 1:
         streams = _time_streams(args, N, torch, dist, world, rank, dev, pol)
     total_steps = n * world * args.steps
     assert int(cnt[N.CNT_STEPS]) == total_steps, (cnt, total_steps)
@@ -609,22 +654,22 @@ def main():
         if streams is not None:
             line["streams"] = streams
         # side legs: reported beside the headline, never allowed to take the bench line down with them
-        if gpu and world == 1 and args.facade_steps > 0:
+        if full and world == 1 and args.facade_steps > 0:
             try:
                 line["facade_single_env"] = time_facade(args.facade_steps, dev)
             except Exception as e:  # noqa: BLE001
                 line["facade_single_env"] = {"error": repr(e)[:300]}
-        if gpu and world == 1 and args.c5_steps > 0:
+        if full and world == 1 and args.c5_steps > 0:
             try:
                 line["c5_round"] = time_c5(n, args.c5_steps, dev)
             except Exception as e:  # noqa: BLE001
                 line["c5_round"] = {"error": repr(e)[:300]}
-        if gpu and world == 1 and args.c4_steps > 0:
+        if full and world == 1 and args.c4_steps > 0:
             try:
                 line["c4_shard"] = time_c4(2 * n, args.c4_steps, args.preroll, args.seed, dev)
             except Exception as e:  # noqa: BLE001
                 line["c4_shard"] = {"error": repr(e)[:300]}
-        if gpu and world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.policy, args.cpu_arenas, args.cpu_preroll, args.cpu_steps,
                                                 args.seed)
         print(json.dumps(line), flush=True)

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 O=gpurun_out/ab_roll
 mkdir -p $O
 declare -A LIB=([base]=hockey-env_amd/hockey_amd/_lib/libhockey_hip.so [r3]=hockey-env_amd/hockey_amd/_lib/exp/libhockey_hip_roll_r3.so [r2]=hockey-env_amd/hockey_amd/_lib/exp/libhockey_hip_roll_r2.so)
-B="--no-cpu-baseline --streams 0 --facade-steps 0 --c5-steps 0 --c4-steps 0"
+B="--full --no-cpu-baseline --streams 0 --facade-steps 0 --c5-steps 0 --c4-steps 0"
 for rep in 1 2; do
   for v in base r3 r2; do
     HK_LIB=${LIB[$v]} timeout -k 10 200 python3 bench.py $B --steps 500 --warmup 50 > $O/bench_${v}_$rep.log 2>&1

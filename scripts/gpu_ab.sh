@@ -16,7 +16,7 @@ if [ "${2:-}" = "tests" ]; then
 fi
 timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --facade-steps 0 --c5-steps 0 --c4-steps 0 \
   --no-cpu-baseline --streams 0 --rollout 0 > "$O/driver_cmd.log" 2>&1 || fail driver $?
-timeout -k 10 300 python3 bench.py --steps 500 --warmup 100 --facade-steps 0 --c5-steps 0 --c4-steps 0 \
+timeout -k 10 300 python3 bench.py --full --steps 500 --warmup 100 --facade-steps 0 --c5-steps 0 --c4-steps 0 \
   --no-cpu-baseline --streams 0 > "$O/bench_long.log" 2>&1 || fail bench_long $?
 python3 - "$O" <<'PY'
 import json, sys

@@ -5,7 +5,7 @@
 #   round    the GPU suite, __graft_entry__.smoke(), then scripts/profile_round.sh (PMC / SQ counter passes, the
 #            driver's bench command, a 500-step bench, rocprofv3 kernel stats, per-wave tail statistics)
 #   tests    the GPU suite only ([pytest -k expression])
-#   bench    bench.py with the given arguments, then rocprofv3 --kernel-trace --stats of the same command
+#   bench    bench.py with the given arguments (pass --full for the side legs), then rocprofv3 --kernel-trace --stats of the same command
 #   noise    scripts/noise_study.py: <protocol> <seed | noise:seed>... -> every noise x seed (or the named pairs)
 #            side by side, one process each; protocol sp_per takes p<0|1>s<0|1>:seed (PER, self-play switches)
 #   learner  scripts/learner_profile.py + rocprofv3 kernel stats of it

@@ -96,6 +96,18 @@ def test_bench_rejects_gpus_world_size_mismatch():
     assert "WORLD_SIZE=2" in err
 
 
+def test_bench_full_flag_and_dump_outputs_in_rehearsal(tmp_path):
+    """--full is accepted everywhere (the rehearsal has no side legs to run); --dump-outputs needs stepped arenas,
+    so the rehearsal refuses it instead of writing nothing."""
+    base = ["--gpus", "1", "--rehearse", "--steps", "3", "--warmup", "1", "--preroll", "0", "--arenas", "64"]
+    rc, lines, err = _bench(base + ["--full"])
+    assert rc == 0 and len(lines) == 1, err[-2000:]
+    assert lines[0]["steps"] == 3 and "ms_per_step" in lines[0] and "cpu_baseline" not in lines[0]
+    rc, lines, err = _bench(base + ["--dump-outputs", str(tmp_path / "out")])
+    assert rc != 0 and not lines and "--dump-outputs" in err
+    assert not (tmp_path / "out").exists()
+
+
 def test_bench_failed_rank_fails_the_launch():
     """A rank that dies makes the launcher exit non-zero (here: an invalid arena count on every rank)."""
     rc, lines, err = _bench(["--gpus", "2", "--rehearse", "--steps", "2", "--warmup", "0", "--preroll", "0",
