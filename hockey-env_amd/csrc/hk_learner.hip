@@ -610,8 +610,13 @@ __device__ __forceinline__ void wgrad_tile(const WgJobs &jobs, int bx, int by, i
     __syncthreads();
     if (sub + SUB < csize) fetch(sub + SUB);
     if (bias && threadIdx.x < OT) {
+      // the sub-chunk's 32 rows as four interleaved partial sums joined as a tree, then added to the chunk's sum:
+      // one running sum over the chunk's 256 or 512 signed terms lost a few ulp more than torch's blocked column
+      // sum does (tests/test_gpu_learner_kernels.py measures both against float64)
+      float ps[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-      for (int r = 0; r < SUB; ++r) bsum += sa[b][r][threadIdx.x];
+      for (int r = 0; r < SUB; ++r) ps[r & 3] += sa[b][r][threadIdx.x];
+      bsum += (ps[0] + ps[1]) + (ps[2] + ps[3]);
     }
 #pragma unroll
     for (int s = 0; s < SUB / 4; ++s) {
@@ -728,9 +733,13 @@ __global__ void __launch_bounds__(256) adam_kernel(hkl_adam_io io) {
     if (io.wd != 0.0f) g += io.wd * p;
     const float t = (float)(*io.step + 1);
     float m = S.m[k], v = S.v[k];
-    m = m + (g - m) * (1.0f - io.beta1);  // exp_avg.lerp_(grad, 1 - beta1)
-    v = v * io.beta2 + (1.0f - io.beta2) * g * g;
-    const float bc1 = 1.0f - powf(io.beta1, t), bc2 = 1.0f - powf(io.beta2, t);
+    // 1 - beta is taken in double and then rounded, as torch rounds its Python scalar: 1.0f - 0.999f is 1.3e-5 off
+    // 0.001 (and 1.0f - 0.9f 2.4e-7 off 0.1), a scale error on every v (m) that no summation order accounts for
+    const float beta1 = (float)io.beta1, beta2 = (float)io.beta2;
+    const float omb1 = (float)(1.0 - io.beta1), omb2 = (float)(1.0 - io.beta2);
+    m = m + (g - m) * omb1;  // exp_avg.lerp_(grad, 1 - beta1)
+    v = v * beta2 + omb2 * g * g;
+    const float bc1 = 1.0f - powf(beta1, t), bc2 = 1.0f - powf(beta2, t);
     const float denom = sqrtf(v) / sqrtf(bc2) + io.eps;
     p = p - (io.lr / bc1) * (m / denom);
     S.m[k] = m;

@@ -67,8 +67,8 @@ class Seg(ctypes.Structure):
 
 
 class AdamIO(ctypes.Structure):
-    _fields_ = [("seg", Seg * MAX_SEG), ("n_seg", ctypes.c_int32), ("lr", ctypes.c_float), ("beta1", ctypes.c_float),
-                ("beta2", ctypes.c_float), ("eps", ctypes.c_float), ("wd", ctypes.c_float), ("step", vp),
+    _fields_ = [("seg", Seg * MAX_SEG), ("n_seg", ctypes.c_int32), ("lr", ctypes.c_float), ("beta1", ctypes.c_double),
+                ("beta2", ctypes.c_double), ("eps", ctypes.c_float), ("wd", ctypes.c_float), ("step", vp),
                 ("loss_src", vp), ("loss_chunks", ctypes.c_int32), ("loss_scale", ctypes.c_float),
                 ("loss_sum", vp), ("loss_count", vp), ("polyak", ctypes.c_int32), ("polyak_rho", ctypes.c_float),
                 ("polyak_tau", ctypes.c_float)]

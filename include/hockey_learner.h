@@ -78,7 +78,9 @@ typedef struct {
 typedef struct {
   hkl_seg seg[HKL_MAX_SEG];
   int32_t n_seg;
-  float lr, beta1, beta2, eps, wd;
+  float lr;
+  double beta1, beta2; /* double: the kernel rounds 1 - beta from it, as torch does from its Python scalars */
+  float eps, wd;
   const int64_t *step;           /* optimiser steps taken so far (device); hkl_pack advances it */
   const float *loss_src;         /* optional: loss partials; *loss_sum += their sum x loss_scale, *loss_count += 1 */
   int32_t loss_chunks;
