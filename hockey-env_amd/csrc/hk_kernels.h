@@ -20,6 +20,8 @@ enum { I_AWAKE = 0, I_HAS1, I_HAS2, I_TIME, I_DONE, I_WINNER, I_MAXT, I_TOUCH, I
 // hk_set_state / hk_reset reject aux / max_t values outside these ranges with HK_E_INVALID (include/hockey.h).
 enum { PW_TAW = 0, PW_ENW, PW_HM, PW_TIME, PW_EPISODE, PW_STEP, NPW };
 constexpr int kHasMax = 255, kMaxTMax = 65535;
+// the touching / enabled masks take one bit per contact pair and the awake word one per dynamic body (bodies below B_WT)
+static_assert(NP <= 27 && B_WT <= 3, "PW_TAW / PW_ENW pack 27 pair bits and 3 awake bits");
 HK_DEV void unpack_ints(const uint32_t (&p)[NPW], int32_t (&iw)[NIF]) {
   iw[I_TOUCH] = (int32_t)(p[PW_TAW] & 0x07ffffffu);
   iw[I_AWAKE] = (int32_t)((p[PW_TAW] >> 27) & 7u);
@@ -86,7 +88,7 @@ struct StepIO {
 };
 
 // hk_step_host's resident server (single-arena contexts): one wave stays on the GPU and serves step requests
-// posted in the context's mapped host buffer, so a step costs no launch.  Protocol (hk_capi.cpp hk_step_host):
+// posted in the context's mapped host buffer, so a step costs no launch.  Protocol (hk_host_step.cpp StepServer):
 // the host writes the inputs and `args`, then the sequence number into `req` (release); the server sees
 // req != its last served number (acquire at system scope), runs the step with args' flags / input pointers,
 // writes the outputs and then the sequence number into `done` (release).  The server exits when `req` holds

@@ -126,6 +126,10 @@ const char *hk_last_error(void);
 const char *hk_version(void);
 
 int hk_create(int device, int64_t n_arenas, const hk_config *cfg, void **ctx_out);
+/* Frees the context.  If its hk_step_host server does not stop within the wait limit (see hk_step_host: the
+ * stream it was started from is still blocked), the context's device arrays and pinned buffer are LEAKED rather
+ * than freed under a kernel that may still touch them, and the call returns HK_E_DEVICE; the handle is invalid
+ * either way. */
 int hk_destroy(void *ctx);
 int64_t hk_num_arenas(const void *ctx);
 int hk_set_policy(void *ctx, int player, int policy);
@@ -135,7 +139,9 @@ int hk_set_policy(void *ctx, int player, int policy);
  * context's mode.  max_t ([N] i32) NULL = mode default (250 NORMAL / 80 training); values outside [0, 65535] are
  * rejected with HK_E_INVALID (checked on the host before any launch; r06 packs max_t into 16 bits).  one_starts ([N] u8)
  * is only read when params == NULL (NORMAL puck side); NULL = toggle the per-arena flag like
- * reset(one_starting=None). */
+ * reset(one_starting=None).
+ * With max_t the call is NOT fire-and-forget: the array is copied to the host on `stream` and the stream is
+ * synchronised for the range check before the reset is launched, so such a call is illegal under stream capture. */
 int hk_reset(void *ctx, const uint8_t *mask, const float *params, const int32_t *max_t,
              const uint8_t *one_starts, void *stream);
 
@@ -146,9 +152,17 @@ int hk_step(void *ctx, const hk_step_io *io, void *stream);
  * the context's pinned, device-mapped buffer and the packed result returns to `out` before the call returns.
  * By default a resident step server does the step: a one-wave kernel that stays on the GPU on a private stream
  * (started on the first call, ordered after the work already on `stream`) and serves each call's request from
- * the mapped buffer, so a step costs no kernel launch.  It exits after 20 ms without a request or 2 s in all and
+ * the mapped buffer, so a step costs no kernel launch.  It exits after 4 ms without a request or 2 s in all and
  * is restarted on demand; every other entry point of the context stops it first, so context calls stay ordered
- * as on one stream.  HK_STEP_HOST_SERVER=0 launches one step kernel per call on `stream` instead (the host waits
+ * as on one stream.
+ * Every wait on the server is bounded by the wait limit (10 s; HK_STEP_HOST_WAIT_MS, read at the context's first
+ * step, replaces it).  A step whose server does not answer in time -- the usual cause is a blocked `stream`, which
+ * the server is ordered after -- withdraws its request, abandons the server and returns HK_E_DEVICE.  The request
+ * may have been taken while it was withdrawn: after THIS error the arena may or may not have advanced one step,
+ * and the caller must hk_reset or hk_set_state it before using it.  While the abandoned server's stream is busy,
+ * every call that has to stop it (a step, reset, state access, ..., destroy) fails with HK_E_DEVICE after at most
+ * the wait limit; other contexts are not held up, and once that stream is idle the context works again.
+ * HK_STEP_HOST_SERVER=0 launches one step kernel per call on `stream` instead (the host waits
  * on a completion word the kernel stores after its last output); HK_STEP_HOST_STAGED=1 stages through device
  * copies (A/B timing).  actions: host [1,8] f32 (NULL if no player is external); opp_inc: host [1,2] f64 or
  * NULL; flags: HK_STEP_* (as hk_step_io.flags); out: host buffer of HK_HOST_RECORD_BYTES = obs f32[18] @0,
@@ -169,7 +183,9 @@ int hk_rollout(void *ctx, int32_t n_steps, const hk_step_io *io, void *stream);
  * arena's int words are packed in HBM (r06; the reference's values are has_puck 0..15, done 0/1, winner -1/0/1).
  * hk_set_state applies pybox2d setter semantics in set_state's order (SetTransform, SetLinearVelocity wakes,
  * ...); a NaN position pair / angle / velocity pair / omega leaves that quantity's setter uncalled (the
- * reference's set_state never assigns the puck's angle or angular velocity, hockey_env.py:594-608). */
+ * reference's set_state never assigns the puck's angle or angular velocity, hockey_env.py:594-608).
+ * hk_set_state with aux copies it to the host on `stream` and synchronises the stream for the check (as hk_reset
+ * with max_t): not fire-and-forget, and illegal under stream capture. */
 int hk_get_state(void *ctx, float *state, int32_t *aux, void *stream);
 int hk_set_state(void *ctx, const uint8_t *mask, const float *state, const int32_t *aux, void *stream);
 

@@ -323,7 +323,7 @@ def test_step_server_survives_idle_gaps_and_interleaved_calls(monkeypatch):
             assert np.array_equal(o1[0], o0[0]) and o1[1] == o0[1] and o1[2] == o0[2] and o1[4] == o0[4], (ep, t)
             assert np.array_equal(envs["1"]._out_np, envs["0"]._out_np), (ep, t)
             if t == 20:
-                time.sleep(0.05)  # past the server's idle limit (hk_capi.cpp kSrvIdleMs)
+                time.sleep(0.05)  # past the server's idle limit (hk_host_step.cpp kSrvIdleMs)
             if t == 30:
                 for env in envs.values():
                     env._vec.get_state()  # a device call between steps
@@ -378,6 +378,85 @@ def test_round_robin_facades_share_one_step_server():
     assert mean_ms < 5.0, mean_ms
     for e in envs + twins:
         e.close()
+
+
+def test_blocked_caller_stream_times_out_without_wedging_other_facades(monkeypatch):
+    """Every wait on the step server is bounded, every time.  With HK_STEP_HOST_WAIT_MS = 40 and the
+    current stream occupied by self-ending work ten times that long (capped at 0.5 s), facade A's step cannot be
+    served (its server is ordered after that stream): it fails with HK_E_DEVICE within a small multiple of the limit,
+    and so do a second step and a reset of A.  Facade B then steps successfully on a stream of its own while A's
+    stream is still busy.  B's step is what the code before this test could not do: after A's time-out A's server
+    stayed recorded as running and as the device slot's owner, so B's hand-over called an unbounded
+    hipStreamSynchronize on the server stream under the device lock and waited out A's stream.
+    After a device synchronise A is usable again: reset brings it back, its next steps equal a twin on the
+    launch-per-step path bit for bit, its step counter shows 0 or 1 steps from the withdrawn request (0: the
+    abandoned server started after the quit word was posted and left without stepping; 1: a server took the request
+    while it was being withdrawn, the case include/hockey.h documents), and both contexts close with HK_OK."""
+    import time
+
+    from hockey_amd.hockey_env import HockeyEnv
+
+    limit_s, E_DEVICE = 0.040, -4
+    bound_s = 5 * limit_s
+    monkeypatch.setenv("HK_STEP_HOST_WAIT_MS", str(int(limit_s * 1e3)))
+    monkeypatch.delenv("HK_STEP_HOST_SERVER", raising=False)
+    monkeypatch.delenv("HK_STEP_HOST_STAGED", raising=False)
+    a, b = HockeyEnv(), HockeyEnv()
+    L = a._vec.L
+    zero = np.zeros(8, np.float32)
+    b.step(zero)  # both contexts have their buffers, and B's server holds the device's slot
+    a.step(zero)
+    a.reset(seed=5)  # stops A's server: its next step has to start one
+    steps0 = int(a._vec.counters()[N.CNT_STEPS])
+
+    def timed(call):
+        t0 = time.perf_counter()
+        rc = call()
+        return rc, time.perf_counter() - t0
+
+    def raw_step(env):
+        act_p, _, out_p = env._host_ptrs
+        return L.hk_step_host(env._vec._ctx, act_p, None, 0, out_p, env._vec._stream())
+
+    torch.cuda._sleep(100_000)  # warm-up, then cycles per second from a short measured run
+    torch.cuda.synchronize()
+    probe = 2_000_000
+    _, probe_s = timed(lambda: (torch.cuda._sleep(probe), torch.cuda.synchronize()))
+    block_s = min(10 * limit_s, 0.5)
+    torch.cuda._sleep(int(probe * block_s / probe_s))  # the current stream is busy for about block_s
+
+    rc, dt = timed(lambda: raw_step(a))
+    assert rc == E_DEVICE and b"wait limit" in L.hk_last_error() and dt < bound_s, (rc, dt, L.hk_last_error())
+    rc, dt = timed(lambda: raw_step(a))
+    assert rc == E_DEVICE and b"wait limit" in L.hk_last_error() and dt < bound_s, (rc, dt, L.hk_last_error())
+    rc, dt = timed(lambda: L.hk_reset(a._vec._ctx, None, None, None, None, a._vec._stream()))
+    assert rc == E_DEVICE and b"wait limit" in L.hk_last_error() and dt < bound_s, (rc, dt, L.hk_last_error())
+    with torch.cuda.stream(torch.cuda.Stream()):
+        rc, dt = timed(lambda: raw_step(b))
+    still_blocked = not torch.cuda.current_stream().query()
+    print(f"blocked stream: probe {probe_s * 1e3:.1f} ms, B's step rc {rc} in {dt * 1e3:.2f} ms, "
+          f"A's stream still busy {still_blocked}")
+    assert rc == 0 and dt < bound_s, (rc, dt, L.hk_last_error())
+    assert still_blocked, "the filler ended before B stepped: the case was not exercised"
+
+    torch.cuda.synchronize()
+    extra = int(a._vec.counters()[N.CNT_STEPS]) - steps0
+    assert extra in (0, 1), extra
+    monkeypatch.setenv("HK_STEP_HOST_SERVER", "0")  # a context picks its step path at its first hk_step_host call
+    twin = HockeyEnv()
+    a.reset(one_starting=True, seed=9)  # explicit: a facade's own resets alternate the starting side
+    twin.reset(one_starting=True, seed=9)
+    rng = np.random.default_rng(9)
+    for t in range(5):
+        act = rng.uniform(-1, 1, 8).astype(np.float32)
+        o, r, d, _, info = a.step(act)
+        o2, r2, d2, _, info2 = twin.step(act)
+        assert np.array_equal(o, o2) and r == r2 and d == d2 and info == info2, t
+        assert np.array_equal(a._out_np, twin._out_np), t
+    torch.cuda.synchronize()
+    for env in (a, b, twin):
+        assert L.hk_destroy(env._vec._ctx) == 0, L.hk_last_error()
+        env._vec._ctx = None
 
 
 def test_keep_mode_step_returns_an_independent_obs():
