@@ -1,4 +1,4 @@
-// hk_hostcheck.cpp -- the per-arena device code (hk_step.h / hk_arena.h / hk_solver.h / hk_geom.h)
+// hk_hostcheck.cpp -- the per-arena device code (hk_step.h / hk_arena.h / hk_solver.h / hk_velocity.h / hk_geom.h)
 // compiled for the host CPU, as a DEBUG AND TEST HARNESS ONLY.
 //
 // It lets the CPU test suite run the kernel's own per-lane logic against the oracle without a GPU, and
@@ -148,7 +148,7 @@ void hkh_flop_events(unsigned long long *out) {
 }
 int hkh_flop_event_count(void) { return hk::EV_N; }
 
-// velocity-loop coverage counters (hk_solver.h HK_HOST_DIAG_INC), process-wide; read and cleared
+// velocity-loop coverage counters (hk_solver.h HK_HOST_DIAG_INC, counted in hk_velocity.h), process-wide; read and cleared
 void hkh_diag(unsigned long long *out4) {
   std::memcpy(out4, hk::g_hk_host_diag, sizeof(hk::g_hk_host_diag));
   std::memset(hk::g_hk_host_diag, 0, sizeof(hk::g_hk_host_diag));

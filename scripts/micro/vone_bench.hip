@@ -1,5 +1,5 @@
 // Microbenchmark (analysis only): cycles per velocity iteration of the one- and two-contact loops of the
-// step kernel's contact solver (hk_solver.h vone_chunk / vtwo_chunk), one wave, 180 iterations, no exit.
+// step kernel's contact solver (hk_velocity.h vone_chunk / vtwo_chunk), one wave, 180 iterations, no exit.
 #include "../../hockey-env_amd/csrc/hk_core.h"
 constexpr hk::Scene g_scene =
 #include "../../hockey-env_amd/csrc/hk_scene_data.inc"

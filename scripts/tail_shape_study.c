@@ -4,7 +4,7 @@
  * stepped (HKO_ARENA_HOOK), runs the bench workload (strong-vs-strong, NORMAL, auto-reset, Philox streams), and
  * records per arena and step its island solves: contact count, the kernel's period-4 exit iteration, and the
  * island's shape (per contact: body A / body B as island-body indices, body A dynamic or static, point count).
- * It then replays the kernel's velocity-family dispatch (hk_solver.h velocity_iterations) over waves of 64
+ * It then replays the kernel's velocity-family dispatch (hk_velocity.h velocity_iterations) over waves of 64
  * consecutive arenas: at every chunk start (iterations 0, 8, 16, 24, 56, 88, 120, 152) the running lanes, their
  * live contact counts and shapes, and so which family the wave runs and whether its running multi-contact lanes
  * share one shape.  Weighted by the chunk's iterations, this says how much of the velocity tail a shape-specialised

@@ -3,7 +3,7 @@
  *
  * For each arena of a batched step (hkov_step) it records up to HKP_MAXSOLVE island solves with at least one
  * contact, in solve order -- the order in which the kernel lays a lane's contacts into its slots:
- *   contact count; the period-4 exit iteration `cur` of the kernel's velocity loops (hk_solver.h): the first
+ *   contact count; the period-4 exit iteration `cur` of the kernel's velocity loops (hk_velocity.h): the first
  *   k = 3 (mod 4), k >= 7, whose state (island body velocities, contact impulses) equals the state at k - 4, plus
  *   1, else 180; per contact (the first 4): island-local body indices iA / iB, whether body A is dynamic, points.
  * and of the step's TOI mini-island solves: how many, the largest, how many of exactly 2 and of more than 2

@@ -1,4 +1,4 @@
-"""Wave-composition zoo on the GPU: the velocity-family dispatch of hk_solver.h under controlled lane mixes.
+"""Wave-composition zoo on the GPU: the velocity-family dispatch of hk_velocity.h under controlled lane mixes.
 
 velocity_iterations / vtwo_family / vone_family pick one of about 25 loop variants from what ALL 64 lanes of a wave
 hold, re-pick at every chunk boundary, let riders discard updates through selects, swap slots and save / restore

@@ -1,4 +1,4 @@
-"""The kernel's per-arena source (hk_step.h -> hk_arena.h / hk_solver.h / hk_geom.h), compiled for the host
+"""The kernel's per-arena source (hk_step.h -> hk_arena.h / hk_solver.h / hk_velocity.h / hk_geom.h), compiled for the host
 CPU by tests/hostcheck.py, held bit-for-bit to the oracle -- on the CPU, without a GPU.
 
 This catches logic errors in the device code before a GPU run; the GPU parity tests (test_gpu_parity.py)
@@ -146,7 +146,7 @@ def test_per_step_opponent_mix_vs_oracle_vec(oracle):
 
 
 def test_island_retirement_and_slot_swaps_vs_oracle(oracle):
-    """Islands of one lane retire one by one inside the shared velocity loop (hk_solver.h vgen / vtwo), and
+    """Islands of one lane retire one by one inside the shared velocity loop (hk_velocity.h vgen / vtwo), and
     the live contacts are swapped into the one- and two-contact slots: both paths run in a bit-exact lockstep
     of the strong-vs-strong workload against the oracle (which solves island by island, like Box2D)."""
     velocity_diag()
@@ -201,7 +201,7 @@ def test_step_record_matches_outputs_and_state(oracle):
 
 
 def test_shape_families_vs_oracle(oracle):
-    """The tail's shape-specialised velocity loops (r06, hk_solver.h): the S2 two-contact chunk (contact 1's body B
+    """The tail's shape-specialised velocity loops (r06, hk_velocity.h): the S2 two-contact chunk (contact 1's body B
     aliased to contact 0's body A, contact 1 static-A) and the S3 three-contact family (wall-puck, player-puck,
     wall-player with the two dynamic bodies in locals) both run in a bit-exact lockstep of the strong-vs-strong
     bench workload against the oracle.  (The host build runs one lane at a time, so the riders and mixed waves of

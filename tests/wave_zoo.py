@@ -1,7 +1,7 @@
 """Wave-composition zoo: scenarios, labels and a dispatch predictor for the step kernel's velocity families.
 TEST INFRASTRUCTURE ONLY -- the product package never loads it.
 
-hk_solver.h picks the velocity loop of a 64-lane wave from what ALL its running lanes hold (velocity_iterations,
+hk_velocity.h picks the velocity loop of a 64-lane wave from what ALL its running lanes hold (velocity_iterations,
 vtwo_family, vone_family: about 25 template instantiations, re-picked at every chunk boundary).  The host build of
 that source runs one lane at a time and cannot reach the mixed-wave paths, so the GPU tests have to -- with the
 mix under control.  This module provides
@@ -264,7 +264,7 @@ def _is_s2(c0, c1):
 def predict(lanes, strict=True):
     """The dispatch of one wave at one step.  lanes: (shape key, cur list) per lane (idle lanes: ("", [])).
 
-    Restates velocity_iterations / vtwo_family / vone_family of hk_solver.h over the lanes' live contacts.  An
+    Restates velocity_iterations / vtwo_family / vone_family of hk_velocity.h over the lanes' live contacts.  An
     island leaves the loops at its `cur` (exit needs the period-4 snapshot match) -- or, where a family switch at
     iteration b restarted the snapshot chain, at max(cur, b + 8); switches happen at chunk boundaries only, so an
     island with cur <= 24 has left by iteration 32 and one with cur >= 100 runs the chunk that starts at 56
