@@ -11,6 +11,9 @@ target noise ``torch.randn_like`` of shape [B, 4] -- so from the same generator 
 the eager update's random numbers (tests/test_gpu_learner.py compares the two).  The optimiser state is the
 learner's own (Adam moments in fp32 device buffers): ``agent.opt_critic`` / ``opt_actor`` are not used.
 
+On a ``hockey_amd.td3.DevicePrioritizedRing`` the prioritized slots, importance weights and the priority write-back are
+the hkl_per_* kernels (per-block float64 sums; the slots come from the Philox stream under rng="device").
+
 Every call is asynchronous on torch's current stream and graph-capturable (fixed buffers, device step counters).
 There is no CPU path: construction fails loudly without the library or a GPU.
 """
@@ -74,9 +77,25 @@ class AdamIO(ctypes.Structure):
                 ("polyak_tau", ctypes.c_float)]
 
 
+class Per(ctypes.Structure):
+    _fields_ = [("cap", ctypes.c_int64), ("w", vp), ("size", vp), ("bsum", vp), ("bmax", vp), ("bpre", vp),
+                ("last", vp), ("bown", vp)]
+
+
+class PerSampleIO(ctypes.Structure):
+    _fields_ = [("per", Per), ("batch", ctypes.c_int64), ("seed", ctypes.c_uint64), ("counter", vp), ("u", vp),
+                ("idx", vp), ("noise", vp), ("scale", ctypes.c_float), ("clip", ctypes.c_float), ("iw", vp),
+                ("beta", ctypes.c_double)]
+
+
+class PerUpdateIO(ctypes.Structure):
+    _fields_ = [("per", Per), ("batch", ctypes.c_int64), ("idx", vp), ("td", vp)]
+
+
 EXPORTS = ["hkl_last_error", "hkl_pack_floats", "hkl_pack", "hkl_critic_step", "hkl_actor_step", "hkl_wgrad",
            "hkl_wgrad_pair",
-           "hkl_adam", "hkl_polyak", "hkl_tanh_probe", "hkl_sample"]
+           "hkl_adam", "hkl_polyak", "hkl_tanh_probe", "hkl_sample", "hkl_per_block", "hkl_per_refresh",
+           "hkl_per_push", "hkl_per_sample", "hkl_per_weights", "hkl_per_update"]
 
 
 def tanh_probe(x):
@@ -108,6 +127,11 @@ def lib():
         L.hkl_polyak.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_float, ctypes.c_float, vp]
         L.hkl_tanh_probe.argtypes = [vp, vp, ctypes.c_int64, vp]
         L.hkl_sample.argtypes = [ctypes.POINTER(SampleIO), vp]
+        L.hkl_per_refresh.argtypes = [ctypes.POINTER(Per), ctypes.c_int64, ctypes.c_int64, vp]
+        L.hkl_per_push.argtypes = [ctypes.POINTER(Per), ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, vp]
+        L.hkl_per_sample.argtypes = [ctypes.POINTER(PerSampleIO), vp]
+        L.hkl_per_weights.argtypes = [ctypes.POINTER(PerSampleIO), vp]
+        L.hkl_per_update.argtypes = [ctypes.POINTER(PerUpdateIO), vp]
         if L.hkl_pack_floats() != PACK_FLOATS:
             raise _native.HockeyNativeError("libhockey_learner.so pack size differs from hockey_amd.learner_hip")
         _lib = L
@@ -210,6 +234,16 @@ class FusedLearner:
         sio.scale, sio.clip = c.target_action_noise_scale, c.target_action_noise_clip
         self.sio = sio
         self.iw = z(B) if ring.prioritized else None
+        # a DevicePrioritizedRing (hockey_amd.td3) samples, weighs and writes back through the hkl_per_* kernels:
+        # psio draws from the learner's Philox stream, psio_u from torch uniforms (rng="torch": noise by torch too)
+        self.psio = self.psio_u = self.puio = None
+        if getattr(ring, "device_sampler", False):
+            self._u = torch.zeros(B, dtype=torch.float64, device=dev)
+            self.psio = PerSampleIO(ring.per, B, sio.seed, sio.counter, None, sio.idx, sio.noise, sio.scale, sio.clip,
+                                    _p(self.iw), ring.beta)
+            self.psio_u = PerSampleIO(ring.per, B, 0, None, _p(self._u), sio.idx, None, 0.0, 0.0, _p(self.iw),
+                                      ring.beta)
+            self.puio = PerUpdateIO(ring.per, B, sio.idx, _p(self.buf["td"]))
         low = agent.critic.action_low.float().cpu().tolist()
         rng = agent.critic.action_range.float().cpu().tolist()
         self._build_io(low, rng)
@@ -324,20 +358,35 @@ class FusedLearner:
         Polyak averaging of both targets.  The batch's slots and target noise come from the device Philox stream
         (rng="device": one kernel), or from torch's generator in the eager learner's order (rng="torch": the slots
         via ring.sample_indices, then N(0, scale) [B, 4]), or (tests) from idx / noise: the slots and the UNCLIPPED
-        N(0, scale) noise."""
+        N(0, scale) noise.  On a DevicePrioritizedRing one hkl_per_sample draws the prioritized slots (from the Philox
+        stream, or under rng="torch" from torch.rand(B, float64)) and writes the importance weights, and one
+        hkl_per_update writes the TD errors back; with idx given, hkl_per_weights weighs those slots."""
         L, st, b = self.L, self._stream(), self.buf
         c = self.cfg
         prioritized = self.ring.prioritized
-        if idx is None and noise is None and self.rng == "device" and not prioritized:
-            _check(L.hkl_sample(ctypes.byref(self.sio), st), "hkl_sample")
+        dev_per = self.psio is not None
+        iw_done = False
+        if idx is None and noise is None and self.rng == "device" and (dev_per or not prioritized):
+            if dev_per:  # slots, target noise and importance weights in one call
+                _check(L.hkl_per_sample(ctypes.byref(self.psio), st), "hkl_per_sample")
+                iw_done = True
+            else:
+                _check(L.hkl_sample(ctypes.byref(self.sio), st), "hkl_sample")
             i = self.idx
         else:
-            i = self.ring.sample_indices(self.B) if idx is None else idx
-            self.idx.copy_(i)
+            if idx is None and dev_per:  # torch's generator in the eager order: the slots' uniforms, then the noise
+                self._u.copy_(torch.rand(self.B, device=self.agent.device, dtype=torch.float64))
+                _check(L.hkl_per_sample(ctypes.byref(self.psio_u), st), "hkl_per_sample")
+                i, iw_done = self.idx, True
+            else:
+                i = self.ring.sample_indices(self.B) if idx is None else idx
+                self.idx.copy_(i)
             if noise is None:
                 noise = torch.randn((self.B, 4), device=self.agent.device) * c.target_action_noise_scale
             b["noise"].copy_(torch.clamp(noise, -c.target_action_noise_clip, c.target_action_noise_clip))
-        if self.iw is not None:
+        if dev_per and not iw_done:  # slots given by the caller
+            _check(L.hkl_per_weights(ctypes.byref(self.psio), st), "hkl_per_weights")
+        elif self.iw is not None and not iw_done:
             wb = self.ring.w[i]
             p = wb / wb.sum()
             iw = (1.0 / (p * self.ring.size_t)) ** self.ring.beta
@@ -349,7 +398,10 @@ class FusedLearner:
         self.adam["critic"].polyak = 1 if train_actor else 0
         _check(L.hkl_adam(ctypes.byref(self.adam["critic"]), st), "hkl_adam")
         self._pack([self.nets["q1"], self.nets["q2"]], self.step["critic"], st)
-        if self.ring.prioritized:
+        if dev_per:
+            self.ring.last = self.idx
+            _check(L.hkl_per_update(ctypes.byref(self.puio), st), "hkl_per_update")
+        elif self.ring.prioritized:
             self.ring.last = i
             self.ring.update_priorities(b["td"])
         if not train_actor:

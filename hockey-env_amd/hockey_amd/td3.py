@@ -12,7 +12,8 @@ Mirrors the reference's learner, acting and collection semantics on device tenso
   replay), delayed actor update every ``policy_update_freq`` critic updates with -Q1 as the actor loss, Polyak
   averaging rho = 1 - tau; Adam(lr, eps 1e-6, weight decay wd) for both (rl/td3/agent.py:174-182);
 * replay: rl/replay/uniform_buffer.py (``ReplayRing``) and rl/replay/prioritized_buffer.py:6-69
-  (``PrioritizedRing``), both device-resident;
+  (``PrioritizedRing``; ``DevicePrioritizedRing`` samples and writes back from per-block sums with HIP kernels
+  instead of passes over the whole ring), all device-resident;
 * acting: rl/td3/agent.py:198-264 -- uniform random actions while the agent's step count is below
   ``start_steps``, then actor + exploration noise of the configured kind (``hockey_amd.noise``: Gaussian, OU,
   pink, uniform; rl/common/noise.py) scaled by the annealed / constant noise scale, clamped to [-1, 1];
@@ -265,6 +266,75 @@ class PrioritizedRing(ReplayRing):
         end = torch.where(is_last, ar, torch.full_like(ar, b))
         end = torch.flip(torch.cummin(torch.flip(end, [0]), 0).values, [0])
         self.w[slot] = torch.clamp(td.detach()[perm[end]], 1e-6, 1e6)
+
+
+class DevicePrioritizedRing(PrioritizedRing):
+    """PrioritizedRing whose push, sampling, importance weights and priority write-back run through the hkl_per_*
+    kernels (include/hockey_learner.h, csrc/hk_learner.hip) on float64 sums per block of ``hkl_per_block()`` slots,
+    instead of passes over all ``cap`` slots: the same ``w`` tensor, the same distribution and write-back rule.
+    ``sample_indices`` draws ``torch.rand(batch, dtype=float64)`` as PrioritizedRing does; the fused learner draws
+    from its own Philox stream instead (FusedLearner, rng="device").  GPU only.  Code that stores to ``w`` itself
+    calls ``refresh()`` afterwards."""
+
+    device_sampler = True
+
+    def __init__(self, capacity, n_obs=18, n_act=4, device="cuda:0", beta=0.15, init_weight=1e8):
+        from . import _native, learner_hip as LH
+        if torch.device(device).type != "cuda":
+            raise _native.HockeyNativeError("the device prioritized replay sampler runs on the GPU only")
+        self._LH, self._L = LH, LH.lib()
+        super().__init__(capacity, n_obs, n_act, device, beta, init_weight)
+        self._slot = None  # the whole-ring passes' arange: not needed here
+        d = self.device
+        nblk = -(-self.cap // self._L.hkl_per_block())
+        self._bsum = torch.zeros(nblk, dtype=torch.float64, device=d)
+        self._bpre = torch.zeros(nblk, dtype=torch.float64, device=d)
+        self._bmax = torch.zeros(nblk, dtype=torch.float32, device=d)
+        self._last = torch.zeros(self.cap, dtype=torch.int32, device=d)
+        self._bown = torch.zeros(nblk, dtype=torch.int32, device=d)
+        p = LH._p
+        self.per = LH.Per(self.cap, p(self.w), p(self.size_t), p(self._bsum), p(self._bmax), p(self._bpre),
+                          p(self._last), p(self._bown))
+        self.iw = None
+        self.refresh()
+
+    def _stream(self):
+        import ctypes
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def refresh(self, lo=0, n=None):
+        """Recompute the block sums that cover slots [lo, lo + n) (default: all) from ``w`` and the fill level."""
+        n = self.cap - lo if n is None else n
+        self._LH._check(self._L.hkl_per_refresh(self.per, lo, n, self._stream()), "hkl_per_refresh")
+
+    def _before_push(self, n):
+        # the pushed blocks' sums are taken against the new fill level, which ReplayRing.push stores afterwards
+        if n > 0:
+            self._LH._check(self._L.hkl_per_push(self.per, self.pos, n, min(self.size + n, self.cap),
+                                                 self._stream()), "hkl_per_push")
+
+    def _draw(self, batch, u):
+        LH = self._LH
+        idx = torch.empty(batch, dtype=torch.int64, device=self.device)
+        iw = torch.empty(batch, dtype=torch.float32, device=self.device)
+        io = LH.PerSampleIO(self.per, batch, 0, None, LH._p(u), LH._p(idx), None, 0.0, 0.0, LH._p(iw), self.beta)
+        LH._check(self._L.hkl_per_sample(io, self._stream()), "hkl_per_sample")
+        self.last, self.iw = idx, iw
+        return idx
+
+    def sample_indices(self, batch):
+        return self._draw(int(batch), torch.rand(batch, device=self.device, dtype=torch.float64))
+
+    def sample(self, batch):
+        i = self.sample_indices(batch)
+        return self.s[i], self.a[i], self.r[i], self.s2[i], self.d[i], self.iw
+
+    def update_priorities(self, td):
+        LH = self._LH
+        i = self.last.contiguous()
+        td = td.detach().float().contiguous()
+        io = LH.PerUpdateIO(self.per, i.numel(), LH._p(i), LH._p(td))
+        LH._check(self._L.hkl_per_update(io, self._stream()), "hkl_per_update")
 
 
 class TD3:
@@ -530,7 +600,7 @@ class Learner:
 def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_per_round=None, mode=Mode.NORMAL,
           curriculum=None, use_self_play=None, self_play_interval=None, pool_size=None, reset="seeded", log=None,
           replay_capacity=None, graphs=True, eval_fn=None, learner_batch=None, timing=False, replay_ratio=None,
-          env=None, on_step=None, episode_end="max_steps", fused="auto", resume_from=None):
+          env=None, on_step=None, episode_end="max_steps", fused="auto", resume_from=None, per_sampler="torch"):
     """Batched TD3 training (rl/training/train.py TD3Trainer.train).  Each round runs ``max_steps`` steps of
     ``n_arenas`` parallel episodes (no break on done), stores every transition, then performs the learner
     updates of those episodes at the replay ratio: ``ratio * n_arenas * max_steps / B`` updates of batch B =
@@ -558,12 +628,18 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
     when every arena's episode has ended.
 
     resume_from: a td3_*.pt path, its npz fixture or a checkpoint dict: rl/main.py:66-67 ``agent.load(resume_from)``
-    before training (all four networks; fresh optimisers, noise schedule and replay)."""
+    before training (all four networks; fresh optimisers, noise schedule and replay).
+
+    per_sampler: with ``cfg.prioritized_replay``, "torch" (default) keeps PrioritizedRing's whole-ring PyTorch
+    sampling and its random stream; "device" uses DevicePrioritizedRing (per-block sums, the hkl_per_* kernels; the
+    fused learner then draws the slots from its Philox stream)."""
     import time
     from .opponents import OpponentMix
     from .vec_env import VecHockeyEnv
 
     cfg = cfg or TD3Config()
+    if per_sampler not in ("torch", "device"):
+        raise ValueError("per_sampler must be 'torch' or 'device'")
     curriculum = cfg.curriculum_name if curriculum is None else curriculum
     use_self_play = cfg.use_self_play if use_self_play is None else use_self_play
     self_play_interval = cfg.self_play_interval if self_play_interval is None else self_play_interval
@@ -578,7 +654,8 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
                            seed=seed)
     mix = OpponentMix(n_arenas, curriculum, use_self_play, self_play_interval, pool_size, device, seed)
     cap = replay_capacity or max(cfg.buffer_size, n_arenas * cfg.max_steps)
-    ring = (PrioritizedRing(cap, device=device, beta=cfg.beta) if cfg.prioritized_replay
+    per_ring = DevicePrioritizedRing if per_sampler == "device" else PrioritizedRing
+    ring = (per_ring(cap, device=device, beta=cfg.beta) if cfg.prioritized_replay
             else ReplayRing(cap, device=device))
     batch = int(learner_batch or cfg.batch_size)
     learner = Learner(agent, ring, batch, graphs=graphs, fused=fused)

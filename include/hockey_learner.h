@@ -134,6 +134,62 @@ typedef struct {
 } hkl_sample_io;
 int hkl_sample(const hkl_sample_io *io, void *stream);
 
+/* ---- prioritized replay (rl/replay/prioritized_buffer.py) on per-block sums: csrc/hk_learner.hip ----
+ * Slot i of the ring has the sanitised weight p_i = max(nan_to_num(w_i, 0, 0, 0), 1e-6f) for i < *size and 0
+ * otherwise; every sum of them is taken in float64 in a fixed order.  The ring's slots are cut into blocks of
+ * HKL_PER_BLOCK; bsum / bmax hold each block's sum of p and its maximum raw weight (NaN propagates, as torch's max),
+ * so that sampling, the priority write-back and a push touch only the blocks they need. */
+#define HKL_PER_BLOCK 1024
+/* with nblk = ceil(cap / HKL_PER_BLOCK): */
+typedef struct {
+  int64_t cap;
+  float *w;            /* [cap] the ring's raw weights */
+  const int64_t *size; /* the ring's fill level */
+  double *bsum;        /* [nblk] */
+  float *bmax;         /* [nblk] */
+  double *bpre;        /* [nblk] scratch: inclusive prefix of bsum (hkl_per_sample rewrites it) */
+  int32_t *last;       /* [cap] scratch, all zero between calls: hkl_per_update's last position + 1 of a slot */
+  int32_t *bown;       /* [nblk] scratch, all zero between calls: the position + 1 that refreshes a touched block */
+} hkl_per;
+
+/* idx[e] = the first slot whose inclusive CDF of p exceeds u_e * sum(p) (searchsorted(..., right=True)), clamped to
+ * *size - 1; u_e = u[e] when u is given, else hkl_sample's 53-bit Philox draw for (seed, e, *counter).  noise
+ * (optional) [B][4]: hkl_sample's clipped target noise for the same (seed, e, *counter), bit for bit.  iw (optional)
+ * [B]: the importance weights (1 / (p_b * *size)) ** beta / their maximum, p_b = w[idx] / sum_batch(w[idx]) on the
+ * raw weights (learner.py:199-210).  Any batch >= 1. */
+typedef struct {
+  hkl_per per;
+  int64_t batch;
+  uint64_t seed;
+  const int64_t *counter; /* required when u is NULL; hkl_critic_step advances it */
+  const double *u;
+  int64_t *idx;
+  float *noise;
+  float scale, clip;
+  float *iw;
+  double beta;
+} hkl_per_sample_io;
+
+/* w[idx[e]] = clamp(td[e], 1e-6, 1e6); of a slot that occurs more than once the last occurrence wins (numpy's
+ * fancy assignment, prioritized_buffer.py:67-69); then bsum / bmax of every touched block are recomputed */
+typedef struct {
+  hkl_per per;
+  int64_t batch;
+  const int64_t *idx;
+  const float *td;
+} hkl_per_update_io;
+
+int hkl_per_block(void);
+/* recompute bsum / bmax of the blocks that cover slots [lo, lo + n); n == cap rebuilds everything */
+int hkl_per_refresh(const hkl_per *per, int64_t lo, int64_t n, void *stream);
+/* PrioritizedRing._before_push: slots pos .. pos + n - 1 (wrapping) get max(w[0 : size_after]) of the weights
+ * before the call; their blocks are recomputed against the fill level size_after (the caller stores it to *size) */
+int hkl_per_push(const hkl_per *per, int64_t pos, int64_t n, int64_t size_after, void *stream);
+int hkl_per_sample(const hkl_per_sample_io *io, void *stream);
+/* hkl_per_sample's importance weights alone, for the slots already in io->idx */
+int hkl_per_weights(const hkl_per_sample_io *io, void *stream);
+int hkl_per_update(const hkl_per_update_io *io, void *stream);
+
 /* y = the kernels' tanh of x (n floats; a test probe of the activation's accuracy) */
 int hkl_tanh_probe(const float *x, float *y, int64_t n, void *stream);
 
