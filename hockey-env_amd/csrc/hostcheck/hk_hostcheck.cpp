@@ -134,6 +134,13 @@ void hkh_observe(void *h, float *obs, float *obs2) {
   for (int64_t a = 0; a < c->n; ++a) observe_lane(c->s, c->cfg, a, obs, obs2);
 }
 
+// BasicOpponent phases [N][3] (DevState::phase is [3][N]): player 1, player 2, player 2's weak bot under an override
+void hkh_phase(void *h, double *out) {
+  HostCtx *c = (HostCtx *)h;
+  for (int64_t a = 0; a < c->n; ++a)
+    for (int r = 0; r < 3; ++r) out[a * 3 + r] = c->phase[(size_t)r * c->n + a];
+}
+
 // raw SoA state (diagnostics): f [NFF][N] floats, i [NPW][N] packed int words
 void hkh_raw(void *h, float **f, int32_t **i) {
   HostCtx *c = (HostCtx *)h;

@@ -32,7 +32,7 @@ def lib():
         L.hkh_create.restype = vp
         L.hkh_create.argtypes = [i64, vp, ctypes.c_uint64, i64]
         for name, n in (("hkh_destroy", 1), ("hkh_reset", 5), ("hkh_step", 2), ("hkh_get_state", 3),
-                        ("hkh_set_state", 4), ("hkh_observe", 3), ("hkh_counters", 2)):
+                        ("hkh_set_state", 4), ("hkh_observe", 3), ("hkh_counters", 2), ("hkh_phase", 2)):
             getattr(L, name).restype = None
             getattr(L, name).argtypes = [vp] * n
         L.hkh_diag.restype = None
@@ -83,9 +83,16 @@ class HostVec:
 
     __del__ = close
 
-    def reset(self, mask=None):
+    def reset(self, mask=None, one_starts=None):
         m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
-        self.L.hkh_reset(self.h, _p(m), None, None, None)
+        o = None if one_starts is None else np.ascontiguousarray(one_starts, np.uint8)
+        self.L.hkh_reset(self.h, _p(m), None, None, _p(o))
+
+    def phase(self):
+        """BasicOpponent phases [N,3]: player 1, player 2, player 2's weak bot under a policy2 override."""
+        out = np.zeros((self.n, 3), np.float64)
+        self.L.hkh_phase(self.h, _p(out))
+        return out
 
     def reset_params(self, params, mask=None, max_t=None):
         p = np.ascontiguousarray(params, np.float32)
