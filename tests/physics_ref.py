@@ -35,6 +35,26 @@ MU_RACKET = float(np.sqrt(0.1 * 1.0))
 Y_TOP, Y_BOT = 7.5 - 1.0 / 6, 0.5 + 1.0 / 6
 X_LEFT, X_RIGHT = 5 - (245.0 / 60 - 1.0 / 6), 5 + (245.0 / 60 - 1.0 / 6)
 MARGIN = 0.05  # clear_of_walls: five skins (2 * linearSlop) beyond touching
+POLY_RADIUS = 0.01  # b2_polygonRadius = 2 * linearSlop: the skin of every polygon
+BAUMGARTE, MAX_CORRECTION, POSITION_ITERATIONS = 0.2, 0.2, 60  # b2_baumgarte, b2_maxLinearCorrection, world.Step's
+# goal boxes (sensor and solid fixture alike): half-size 10/60 x 75/60, centred at x = 5 -+ 245/60 -+ 10/60, y = 4
+GOAL_HALF = (10.0 / 60, 75.0 / 60)
+GOAL_CENTRE = ((5 - 245.0 / 60 - 10.0 / 60, 4.0), (5 + 245.0 / 60 + 10.0 / 60, 4.0))  # left (winner -1), right (+1)
+# the posts' inner faces x = X_LEFT / X_RIGHT run from the wall down / up to this height (hockey_env.py:222-319: the
+# post quad's inner vertex lies 128/60 from the wall body's centre line, the outer one 135/60)
+POST_Y_BOT, POST_Y_TOP = 0.5 + 128.0 / 60, 7.5 - 128.0 / 60
+POST_Y_BOT_OUTER, POST_Y_TOP_OUTER = 0.5 + 135.0 / 60, 7.5 - 135.0 / 60  # ... and 20/60 further out it ends here
+
+
+def post_slant_face(right, up):
+    """The post quad's face towards the goal mouth (hockey_env.py:222-319: the quad (-10, 135), (10, 128), (10, -5),
+    (-10, -5) / 60 about (5 -+ 245/60, 0.5), mirrored for the other three): (inner end, outer end, unit normal into
+    the mouth).  It slants by atan(7 / 20) = 19.3 degrees; the goal box covers its outer half."""
+    inner = np.array([X_RIGHT if right else X_LEFT, POST_Y_TOP if up else POST_Y_BOT])
+    outer = np.array([inner[0] + (1.0 if right else -1.0) / 3, POST_Y_TOP_OUTER if up else POST_Y_BOT_OUTER])
+    d = outer - inner
+    n = np.array([-d[1], d[0]]) / np.hypot(*d)
+    return inner, outer, n if (n[1] > 0) != up else -n
 
 
 def bodies(s):
@@ -162,3 +182,85 @@ def head_on(v_in, m_racket):
     (puck velocity, racket velocity) after the hit."""
     e = restitution(v_in)
     return v_in * (M[2] - e * m_racket) / (M[2] + m_racket), v_in * M[2] * (1 + e) / (M[2] + m_racket)
+
+
+# A sequential-impulse solve rounds each velocity twice per iteration (friction row, normal row) by up to half an ulp,
+# for up to 180 iterations; errors of random sign add as a random walk, sqrt(360) / 2 ~ 10 ulps.  Allow 16.
+SOLVER_ULPS = 16
+
+
+# ------------------------------------------------- a racket against static faces (families G, H of physics_scenes2)
+def racket_world(s, who):
+    """World positions of racket `who`'s vertices [N,nv,2] and of its centre of mass [N,2] at state s."""
+    o, a, _, _ = bodies(s)
+    verts = o[:, who, None, :] + _rot(a[:, who, None], VERTS[who][None])
+    return verts, o[:, who] + _rot(a[:, who], LC[who][None])
+
+
+def face_coordinates(p, q, n):
+    """Points p[..., 2] in the frame of a static face through q with unit normal n pointing into the rink:
+    (tau along t = (n_y, -n_x), eta above the face)."""
+    d = np.asarray(p, np.float64) - np.asarray(q, np.float64)
+    return d[..., 0] * n[1] - d[..., 1] * n[0], d[..., 0] * n[0] + d[..., 1] * n[1]
+
+
+def racket_impulse(who, vstar, wstar, s1):
+    """What the step's contacts gave racket `who`: J = m (v' - v*) [N,2] and L = I (omega' - omega*) [N]."""
+    _, _, v1, w1 = bodies(s1)
+    return M[who] * (v1[:, who] - vstar[:, who]), I[who] * (w1[:, who] - wstar[:, who])
+
+
+def point_velocity(who, s0, s1, p):
+    """Velocity after the step of the racket's material points p[N,k,2] (world positions at the START of the step,
+    where Box2D takes its lever arms): v' + omega' x r, r = p - centre of mass."""
+    _, com = racket_world(s0, who)
+    _, _, v1, w1 = bodies(s1)
+    r = p - com[:, None, :]
+    return v1[:, who, None, :] + w1[:, who, None, None] * np.stack([-r[..., 1], r[..., 0]], -1)
+
+
+def centre_of_pressure(who, s0, s1, vstar, wstar, q, n, eta=0.5 * POLY_RADIUS, eta_bar=2 * POLY_RADIUS):
+    """Where along the face (tau) the net impulse acted, from L = r x J with the contact plane at height eta above
+    the face: Box2D puts a manifold point midway between the two skins' surfaces, both within 2 * polygonRadius of
+    the face.  Returns (tau[N], bar[N], J_n[N], J_t[N]); bar is the scene's own error bar: SOLVER_ULPS float32 ulps
+    of each velocity that enters (v', omega', and the v*, omega* the solver held in float32), one of the position,
+    plus |J_t| eta_bar of height uncertainty -- all over J_n."""
+    n = np.asarray(n, np.float64)
+    t = np.array([n[1], -n[0]])
+    chi = t[0] * n[1] - t[1] * n[0]  # t x n
+    J, L = racket_impulse(who, vstar, wstar, s1)
+    Jn, Jt = J @ n, J @ t
+    _, com = racket_world(s0, who)
+    c_tau, c_eta = face_coordinates(com, q, n)
+    _, _, v1, w1 = bodies(s1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        tau = c_tau + (L / chi + (eta - c_eta) * Jt) / Jn
+        ulp = lambda x: np.spacing(np.abs(x).astype(np.float32)).astype(np.float64)  # noqa: E731
+        uv = SOLVER_ULPS * np.maximum(ulp(v1[:, who]), ulp(vstar[:, who])).max(-1)
+        uw = SOLVER_ULPS * np.maximum(ulp(w1[:, who]), ulp(wstar[:, who]))
+        bar = (I[who] * uw + (np.abs(eta - c_eta) + np.abs(tau - c_tau)) * M[who] * uv + np.abs(Jt) * eta_bar) / Jn
+    return tau, bar + float(np.spacing(np.float32(10.0))), Jn, Jt
+
+
+# ------------------------------------------------------------------------ the position solver (family P)
+def position_recurrence(s):
+    """Separation after one step's position solve of a lone dynamic-dynamic contact on the line of centres, both
+    bodies free to move, no rotation: every iteration moves the pair apart by -C, C = clamp(baumgarte (s + linearSlop),
+    -maxLinearCorrection, 0), and the loop ends after the iteration that saw s >= -3 linearSlop (that iteration's
+    correction still applies), at most world.Step's 60 times."""
+    s = float(s)
+    for _ in range(POSITION_ITERATIONS):
+        pre = s
+        s -= min(max(BAUMGARTE * (s + LINEAR_SLOP), -MAX_CORRECTION), 0.0)
+        if pre >= -3 * LINEAR_SLOP:
+            break
+    return s
+
+
+# ------------------------------------------------------------------------------- the goal sensors (family Q)
+def goal_separation(p, goal):
+    """Euclidean distance of the points p[..., 2] from goal box `goal` (0 left, 1 right), less the puck's radius and
+    the box's polygon skin: Box2D's b2TestOverlap of a circle and a polygon is true where this is negative."""
+    p = np.asarray(p, np.float64)
+    d = np.maximum(np.abs(p - np.array(GOAL_CENTRE[goal])) - np.array(GOAL_HALF), 0.0)
+    return np.hypot(d[..., 0], d[..., 1]) - R - POLY_RADIUS

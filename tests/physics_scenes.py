@@ -334,11 +334,14 @@ def check(m, full=True):
     assert m["F_out"] <= 0.0, ("F containment", m["F_out"])
 
 
-def run(env, batch):
-    """Drive any context with set_state / step(actions, debug) / get_state through the batch; numpy in and out."""
+def run(env, batch, aux=False):
+    """Drive any context with set_state / step(actions, debug) / get_state through the batch; numpy in and out.
+    aux=True: also the aux rows before / after each step (env.get_aux), as a third array."""
     env.set_state(batch.state, batch.aux)
-    S, D = [batch.state.copy()], []
+    S, D, A = [batch.state.copy()], [], [batch.aux.copy()]
     for k in range(K):
         D.append(env.step_debug(batch.actions[k]))
         S.append(env.get_state())
-    return np.stack(S), np.stack(D)
+        if aux:
+            A.append(env.get_aux())
+    return (np.stack(S), np.stack(D), np.stack(A)) if aux else (np.stack(S), np.stack(D))

@@ -1,0 +1,631 @@
+"""Seeded scenes for the float64 laws of tests/physics_ref.py that physics_scenes' families A-F leave out: a racket
+against static polygons, the position solver, and the goal sensors.  Same conventions as physics_scenes (a scene is a
+raw state put in place with set_state, then K steps with `debug`); a second batch class with its own seeded generator,
+so physics_scenes.Batch and the tolerances measured on it stay what they were.  Families:
+  G1 / G2  player 1's / player 2's racket closing on the top or bottom wall: half with an edge flat on the wall (a
+           two-point manifold, the block solver), half tilted up to 0.6 rad (one point); random tangential speed, spin
+           and actions
+  H        a racket in a rink corner (a wall and a post's inner face: two manifolds in one island), and a racket
+           against a goal's solid box from inside the goal mouth; both rackets, all four corners, both goals
+           ... and a square corner of the racket on a post's slanted face inside the goal mouth, the one static face
+           that is not axis-aligned
+  S        the racket's flat face drives a resting puck into the top or bottom wall at under 1 m/s: a wall-puck-racket
+           island with a 58 : 1 mass ratio
+  P        a puck at rest overlapping a racket at rest: on the axis through the racket's centre of mass (the position
+           solver's closed form, six depths), and off it (its lever arms); and racket overlapping racket across the
+           centre line, the one position constraint in which both bodies have a lever arm
+  Q        a puck drifting into a goal: through the mouth onto the front face, from behind onto a corner of the box,
+           along the back face, grazing past a corner, and fast enough to jump the box between two steps
+measure() reduces a trajectory (states, debug rows, aux rows) to worst deviations and coverage counts; check() holds
+them to the tolerances below.  numpy only.
+"""
+import numpy as np
+
+import physics_ref as P
+from physics_scenes import HOME, K, PUCK_PARK, TOL as TOL_AF, run as run_af
+
+ETA_MARGIN = 1e-4    # a vertex this close to the 2 * polygonRadius contact margin may or may not be a manifold point
+DRIFT_MARGIN = 3e-6  # six float32 ulps of a position in the rink: what c' - c - dt v' resolves
+FACE_MARGIN = 0.02   # ... and so may one this close to the end of a face of finite length
+G3_MIN_JN = 1.0      # N s (a 58 kg racket stopped from 17 mm/s): below it the centre of pressure has no arm
+NEAR_CONE = 0.98
+P_DEPTHS = (-0.002, -0.01, -0.04, -0.09, -0.14, -0.19)  # separation = face-to-centre gap - r - polygonRadius
+P_OFFSETS = (-0.27, -0.15, 0.12, 0.3)                   # off-axis: the puck's y offset from the racket's centre of mass
+Q_PROBES = (-5e-3, -1e-3, 1e-3, 5e-3)                   # the deciding end-of-step separation
+Q_BAND = 1e-5  # float32 positions cannot decide a goal closer to the threshold than this
+
+# Tolerances: 4 x the worst deviation of the CPU oracle from the float64 model over ten batches of other seeds
+# (1000-1009) and the committed seed 0, as in physics_scenes; DESIGN.md "Float64 rigid-body laws" has the table.
+# Laws with a per-scene error bar (G_cp) and the goal law (Q: an exclusion band instead) have no entry.
+TOL = {
+    "G_approach": 4 * 3.7e-6,   # worst 3.7e-6 m/s of a touching vertex's velocity into the wall after the step
+    "G_push": 4 * 2.3e-7,       # worst 2.3e-7 of -J_n / m
+    # worst 1.8e-5 of the distance of J / m outside the friction cone.  5.6e-6 over the steps in which the oracle counts
+    # no time-of-impact event; the rest are steps with one, whose sub-step Box2D solves with 8 iterations, not 180
+    "G_cone": 4 * 1.8e-5,
+    "G_energy": 4 * 1.3e-7,     # kinetic energy never rose by more than 1.3e-7 relative
+    # H's non-approach is not rounding: nine batches in eleven stay under 3e-6, the others reach 9.9e-5 and 7.6e-3,
+    # a vertex wedged into a corner, two manifolds sharing 180 iterations.  The oracle counts NO time-of-impact event
+    # in the 7.6e-3 step, so this is the converged state of the regular solve and not a leak of the arrival filter.
+    "H_approach": 4 * 7.7e-3,
+    "H_push": 4 * 2.8e-7,       # worst 2.8e-7 (a corner: of -J . (n1 + n2) / m)
+    "H_cone": 4 * 6.0e-6,       # worst 6.0e-6 outside the cone spanned by the touching faces' friction cones
+    "H_energy": 4 * 4.3e-8,     # worst 4.3e-8
+    # worst 4.3e-2 m/s of the puck's velocity into the wall or into the racket's face after the first trapped step: a
+    # 58 : 1 mass ratio in one island converges slowly.  VAR_ITERS_8_3 leaves 2.6 m/s on the committed batch, 15 x
+    "S_approach": 4 * 4.3e-2,
+    "P_recurrence": 4 * 8.1e-7,  # worst 8.1e-7 m of the separation after a step against the closed form
+    "P_momentum": 4 * 7.9e-5,   # worst 7.9e-5 kg m of |sum m dc|: 58 kg times three float32 ulps of x = 7.5
+    # worst 9.3e-3 kg m^2 of |sum m c x dc + I d_angle| about the pair's midpoint, on the racket-racket scenes: the
+    # residual is second order in the correction (the second iteration's arms are the moved ones); puck-racket 8.5e-5
+    "P_angular": 4 * 9.3e-3,
+    # Reasoned, not measured (the oracle's worst is exactly 0): one float32 ulp of a rink coordinate.
+    "P_off_axis": float(np.spacing(np.float32(8.0))),
+}
+# about half of what the oracle yields on the committed seed
+MIN_COUNTS = {"G1_top_one": 11, "G1_top_two": 14, "G1_bottom_one": 11, "G1_bottom_two": 13, "G2_top_one": 12,
+              "G2_top_two": 13, "G2_bottom_one": 10, "G2_bottom_two": 13, "G_cp": 95, "G_near_cone": 57,
+              "H_corner_both": 31, "H_goal": 29, "H_post": 24, "H_near_cone": 30, "S_trapped": 24,
+              "P_off_moved": 40, "P_rackets_moved": 16,
+              "Q0_score_minus": 9, "Q0_score_plus": 6, "Q0_graze": 4, "Q0_tunnel": 2, "Q0_corner": 6, "Q0_face": 6,
+              "Q1_score_minus": 7, "Q1_score_plus": 6, "Q1_graze": 4, "Q1_tunnel": 2, "Q1_corner": 6, "Q1_face": 6}
+MAX_DROPPED = 0.10
+
+
+def _row(p1, p2, pk):
+    return np.concatenate([np.asarray(p1, np.float64), np.asarray(p2, np.float64), np.asarray(pk, np.float64)])
+
+
+def _parked(i):
+    return np.array([HOME[i][0], HOME[i][1], 0, 0, 0, 0], np.float64)
+
+
+_PUCK = np.array([PUCK_PARK[0], PUCK_PARK[1], 0, 0, 0, 0], np.float64)
+
+
+def _world_verts(who, a):
+    c, s = np.cos(a), np.sin(a)
+    return P.VERTS[who] @ np.array([[c, s], [-s, c]])
+
+
+class Batch2:
+    """state[N,18], aux[N,5], actions[K,N,8] and per-arena labels, the families interleaved by a seeded shuffle.
+    Per arena: who (the racket of G / H / P), faces (up to two static faces (q, n, tau_lo, tau_hi) of G / H), tag
+    (P: the separation put in place, Q: the probe aimed at), goal and kind (Q)."""
+
+    def __init__(self, seed=0, scale=1):
+        rng = np.random.default_rng([seed, 2])
+        rows = []
+        for who in (0, 1):
+            for wall in (+1, -1):
+                rows += _family_g(rng, who, wall, 50 * scale)
+        rows += _family_h(rng, 16 * scale) + _family_h_post(rng, 12 * scale) + _family_s(rng, 12 * scale)
+        rows += _family_p(3) + _family_q(rng, 3 * scale)
+        rows += _family_g(rng, 0, +1, 1)  # a count that is no multiple of 64
+        order = rng.permutation(len(rows))
+        rows = [rows[i] for i in order]
+        self.keep_mode = False
+        self.n = len(rows)
+        self.family = np.array([r["family"] for r in rows])
+        self.state = np.array([r["state"] for r in rows], np.float32)
+        self.who = np.array([r.get("who", 0) for r in rows])
+        self.faces = [r.get("faces", ()) for r in rows]
+        self.tag = np.array([r.get("tag", 0.0) for r in rows], np.float64)
+        self.goal = np.array([r.get("goal", 0) for r in rows])
+        self.kind = np.array([r.get("kind", "") for r in rows])
+        self.aux = np.zeros((self.n, 5), np.int32)
+        self.actions = rng.uniform(-1, 1, (K, self.n, 8)).astype(np.float32)
+        self.actions[:, np.isin(self.family, ("P", "Q", "S"))] = 0.0
+        for a in (self.state, self.aux, self.actions):
+            a.setflags(write=False)
+        # Q: no scene may sit where float32 cannot decide it; checked here in float64 on the model trajectory (the
+        # puck's 0.05 / 10 damping below / above 25 m/s) and again by measure() on the states a runner produced
+        q = self.family == "Q"
+        traj = _q_model(self.state[q][:, 12:14].astype(np.float64), self.state[q][:, 15:17].astype(np.float64))
+        sep = np.stack([P.goal_separation(traj[:, i], g) for i, g in enumerate(self.goal[q])], 1)
+        assert np.abs(sep).min() > Q_BAND, np.abs(sep).min()
+        assert (sep[0] >= 0.3).all(), sep[0].min()  # drifts in over several steps; never teleported into overlap
+
+
+# ------------------------------------------------------------------------------------------------------ G and H
+def _racket_state(who, rk):
+    return _row(rk, _parked(1), _PUCK) if who == 0 else _row(_parked(0), rk, _PUCK)
+
+
+def _family_g(rng, who, wall, n):
+    """The wall's face: q on it, n into the rink (top wall: down)."""
+    nrm = np.array([0.0, -float(wall)])
+    y_face = P.Y_TOP if wall > 0 else P.Y_BOT
+    face = ((5.0, y_face), tuple(nrm), -np.inf, np.inf)
+    v = P.VERTS[who]
+    rows = []
+    for k in range(n):
+        u = rng.uniform
+        e = int(rng.integers(len(v)))
+        edge = v[(e + 1) % len(v)] - v[e]
+        out = np.array([edge[1], -edge[0]])  # outward normal of a counter-clockwise polygon's edge
+        tilt = u(-0.002, 0.002) if k % 2 == 0 else rng.choice([-1, 1]) * u(0.12, 0.6)
+        a = np.arctan2(-nrm[1], -nrm[0]) - np.arctan2(out[1], out[0]) + tilt
+        a = (a + np.pi) % (2 * np.pi) - np.pi
+        vw = _world_verts(who, a)
+        gap = u(0.0, 0.015)
+        x = u(2.0, 4.0) if who == 0 else u(6.0, 8.0)
+        y = y_face - wall * gap - (wall * vw[:, 1]).max() * wall
+        rk = [x, y, a, u(-3, 3), wall * u(0.5, 6.0), u(-5, 5)]
+        rows.append(dict(family="G%d" % (who + 1), state=_racket_state(who, rk), who=who, faces=(face,),
+                         tag=float(wall)))
+    return rows
+
+
+def _family_h(rng, n):
+    rows = []
+    for k in range(8 * n):
+        u = rng.uniform
+        who, up = k % 2, (k // 2) % 2
+        sx = -1.0 if who == 0 else 1.0     # which side of the rink: each racket in the corners of its own half
+        sy = 1.0 if up else -1.0
+        xf, yf = (P.X_LEFT, P.X_RIGHT)[who], (P.Y_TOP if up else P.Y_BOT)
+        a = u(-np.pi, np.pi)
+        vw = _world_verts(who, a)
+        if (k // 4) % 2 == 0:  # a corner: the wall, and the post's inner face between the wall and the goal mouth
+            post_end = P.POST_Y_TOP if up else P.POST_Y_BOT
+            t_post = sorted(P.face_coordinates(np.array([[xf, yf], [xf, post_end]]), (xf, yf), (-sx, 0.0))[0])
+            t_wall = sorted(P.face_coordinates(np.array([[xf, yf], [5.0, yf]]), (xf, yf), (0.0, -sy))[0])
+            faces = (((xf, yf), (0.0, -sy), t_wall[0], t_wall[1]), ((xf, yf), (-sx, 0.0), t_post[0], t_post[1]))
+            x = xf - sx * u(0.0, 0.015) - (sx * vw[:, 0]).max() * sx
+            y = yf - sy * u(0.0, 0.015) - (sy * vw[:, 1]).max() * sy
+            rk = [x, y, a, sx * u(0.5, 3.0), sy * u(0.5, 3.0), u(-3, 3)]
+            kind = "corner"
+        else:  # its own goal's solid box from inside the goal mouth (the env's laws turn a racket back that is past
+            g = who  # the centre line by rewriting its velocity, so the far goal is out of a racket's reach)
+            gs = -1.0 if g == 0 else 1.0
+            xg = P.GOAL_CENTRE[g][0] - gs * P.GOAL_HALF[0]  # the box's face towards the rink
+            lo, hi = P.GOAL_CENTRE[g][1] - P.GOAL_HALF[1], P.GOAL_CENTRE[g][1] + P.GOAL_HALF[1]
+            t_goal = sorted(P.face_coordinates(np.array([[xg, lo], [xg, hi]]), (xg, 4.0), (-gs, 0.0))[0])
+            faces = (((xg, 4.0), (-gs, 0.0), t_goal[0], t_goal[1]),)
+            x = xg - gs * u(0.0, 0.015) - (gs * vw[:, 0]).max() * gs
+            rk = [x, u(3.5, 4.5), a, gs * u(0.5, 3.0), u(-2, 2), u(-3, 3)]
+            kind = "goal"
+        rows.append(dict(family="H", state=_racket_state(who, rk), who=who, faces=faces, kind=kind))
+    return rows
+
+
+def _segment_distance(p, a, b):
+    """Distance of the points p[..., 2] from the segment a-b."""
+    d = b - a
+    t = np.clip(((p - a) @ d) / (d @ d), 0.0, 1.0)
+    return np.linalg.norm(p - a - t[..., None] * d, axis=-1)
+
+
+def _family_h_post(rng, n):
+    """A square corner of the racket's flat face pressed onto a post's slanted face inside the goal mouth: the one
+    static face of the scene that is not axis-aligned.  Only the 0.18 m between the post's inner vertex and the goal
+    box's front face can be reached, so every draw is checked in float64: the racket's outline stays 0.035 clear of
+    the goal box and of the post's inner vertex and inner face (no second manifold, no vertex-on-racket-edge contact),
+    and one vertex alone is within the contact margin.  Draws that are not are drawn again."""
+    rows = []
+    k = 0
+    while len(rows) < 4 * n:
+        u = rng.uniform
+        who, up = k % 2, (k // 2) % 2
+        inner, outer, nrm = P.post_slant_face(bool(who), bool(up))
+        t = np.array([nrm[1], -nrm[0]])
+        tau_outer = float((outer - inner) @ t)
+        # the square corner (+-0.1, -+0.4): its outward bisector turned onto -n, then tilted by up to 0.35 rad
+        corner = int(rng.integers(2))
+        v = P.VERTS[who]
+        j = int(np.argmin(np.abs(v[:, 0] - (0.1 if who == 0 else -0.1)) + np.abs(v[:, 1] - (0.4 if corner else -0.4))))
+        e0, e1 = v[j] - v[j - 1], v[(j + 1) % len(v)] - v[j]
+        bis = e0 / np.hypot(*e0) - e1 / np.hypot(*e1)
+        a = np.arctan2(-nrm[1], -nrm[0]) - np.arctan2(bis[1], bis[0]) + u(-0.35, 0.35)
+        a = (a + np.pi) % (2 * np.pi) - np.pi
+        vw = _world_verts(who, a)
+        touch = inner + u(0.04, 0.17) * np.sign(tau_outer) * t + u(0.0, 0.015) * nrm
+        origin = touch - vw[j]
+        poly = origin + vw
+        outline = np.concatenate([poly[m] + np.linspace(0, 1, 80)[:, None] * (poly[(m + 1) % len(poly)] - poly[m])
+                                  for m in range(len(poly))])
+        g = who
+        box = np.maximum(np.abs(outline - np.array(P.GOAL_CENTRE[g])) - np.array(P.GOAL_HALF), 0.0)
+        wall_y = P.Y_TOP if up else P.Y_BOT
+        ok = np.hypot(box[:, 0], box[:, 1]).min() > 0.035
+        ok &= _segment_distance(outline, inner, np.array([inner[0], wall_y])).min() > 0.035
+        eta = P.face_coordinates(poly, inner, nrm)[1]
+        ok &= (eta < 0.035).sum() == 1
+        k += 1
+        if not ok:
+            continue
+        sy = 1.0 if up else -1.0
+        vel = -u(0.5, 3.0) * nrm + u(-1, 1) * t
+        rk = [origin[0], origin[1], a, vel[0], vel[1], u(-3, 3)]
+        face = (tuple(inner), tuple(nrm), min(0.0, tau_outer), max(0.0, tau_outer))
+        rows.append(dict(family="H", state=_racket_state(who, rk), who=who, faces=(face,), kind="post", tag=sy))
+    return rows
+
+
+# ------------------------------------------------------------------------------------------------------------ S
+S_SPAN_MARGIN = 0.1  # the puck's centre stays this far inside the ends of the racket's 0.8 m face
+
+
+def _family_s(rng, n):
+    """The racket's flat face, turned towards the top or bottom wall, drives a resting puck into it at under the
+    1 m/s restitution threshold: wall, puck and racket in one island, both gaps inside the skins."""
+    rows = []
+    for k in range(4 * n):
+        u = rng.uniform
+        who, wall = k % 2, (1.0 if (k // 2) % 2 == 0 else -1.0)
+        sgn = 1.0 if who == 0 else -1.0              # the flat face looks along sgn * x in the racket's frame
+        a = wall * sgn * np.pi / 2 + u(-0.03, 0.03)  # ... and now towards the wall
+        nf = sgn * np.array([np.cos(a), np.sin(a)])  # the face's normal
+        tf = np.array([-nf[1], nf[0]])
+        y_face = P.Y_TOP if wall > 0 else P.Y_BOT
+        pk = np.array([u(2.0, 4.0) if who == 0 else u(6.0, 8.0), y_face - wall * (P.R + u(0.0, 0.008))])
+        foot = pk - (P.R + u(0.0, 0.008)) * nf        # the puck centre's foot on the face
+        origin = foot - 0.1 * nf - u(-0.4 + S_SPAN_MARGIN + 0.05, 0.4 - S_SPAN_MARGIN - 0.05) * tf
+        rk = [origin[0], origin[1], a, u(-0.3, 0.3), wall * u(0.2, 0.9), u(-0.5, 0.5)]
+        puck = [pk[0], pk[1], 0.0, u(-0.3, 0.3), 0.0, u(-5, 5)]
+        st = _row(rk, _parked(1), puck) if who == 0 else _row(_parked(0), rk, puck)
+        rows.append(dict(family="S", state=st, who=who, tag=wall))
+    return rows
+
+
+# ------------------------------------------------------------------------------------------------------------ P
+def _family_p(copies):
+    rows = []
+    for who in (0, 1):
+        sgn = 1.0 if who == 0 else -1.0  # player 1's flat face looks along +x, player 2's along -x
+        for c in range(copies):
+            y0 = 3.0 + c
+            rk = np.array([2.5 if who == 0 else 7.5, y0, 0, 0, 0, 0])
+            for s in P_DEPTHS:
+                for off in (0.0,) + P_OFFSETS[c::copies]:
+                    pk = [rk[0] + sgn * (0.1 + P.POLY_RADIUS + P.R + s), y0 + P.LC[who, 1] + off, 0, 0, 0, 0]
+                    st = _row(rk, _parked(1), pk) if who == 0 else _row(_parked(0), rk, pk)
+                    rows.append(dict(family="P", state=st, who=who, tag=s, kind="axis" if off == 0.0 else "off"))
+    # racket against racket across the centre line, flat face on flat face, offset in y and slightly turned: the
+    # only position constraints in which BOTH bodies have a lever arm (a circle's contact point is its centre)
+    for c in range(copies):
+        for s in P_DEPTHS[1:]:
+            for off in P_OFFSETS[c::copies]:
+                a2 = 0.04 * (1 if off > 0 else -1)
+                reach = _world_verts(1, a2)[:, 0].min()  # player 2's face corner nearest the line
+                p1 = [5.0 - 0.1 - P.POLY_RADIUS - s / 2, 3.0 + c, 0, 0, 0, 0]
+                p2 = [5.0 + P.POLY_RADIUS + s / 2 - reach, 3.0 + c + off, a2, 0, 0, 0]
+                rows.append(dict(family="P", state=_row(p1, p2, _PUCK), who=0, tag=s, kind="rackets"))
+    return rows
+
+
+def p_separation(s, who):
+    """Separation of the puck from racket `who`'s flat face, its skin included (float64): the racket's angle is read,
+    so a racket the correction turned is measured along its own face normal."""
+    o, a, _, _ = P.bodies(s)
+    sgn = 1.0 if who == 0 else -1.0
+    nrm = sgn * np.stack([np.cos(a[:, who]), np.sin(a[:, who])], -1)
+    return ((o[:, 2] - o[:, who]) * nrm).sum(-1) - 0.1 - P.POLY_RADIUS - P.R
+
+
+# ------------------------------------------------------------------------------------------------------------ Q
+def _q_model(p, v):
+    """Free flight of the puck under _limit_puck_speed's damping: positions [K+1, n, 2]."""
+    out = [p]
+    for _ in range(K):
+        ld = np.where(np.hypot(v[:, 0], v[:, 1]) > 25.0, 10.0, 0.05)[:, None]
+        v = v / (1 + P.DT * ld)
+        p = p + P.DT * v
+        out.append(p)
+    return np.stack(out)
+
+
+def _q_travel(speed, steps):
+    """Distance the model puck travels in its first `steps` steps."""
+    d = _q_model(np.zeros((1, 2)), np.array([[speed, 0.0]]))
+    return float(d[steps, 0, 0])
+
+
+def _family_q(rng, n):
+    rows = []
+    rho = P.R + P.POLY_RADIUS
+    for g in (0, 1):
+        gs = -1.0 if g == 0 else 1.0  # the goal lies towards gs * x
+        cx, cy = P.GOAL_CENTRE[g]
+        front, back = cx - gs * P.GOAL_HALF[0], cx + gs * P.GOAL_HALF[0]
+
+        def add(kind, p, v, probe, g=g):
+            rows.append(dict(family="Q", state=_row(_parked(0), _parked(1), [p[0], p[1], 0.0, v[0], v[1], 0.0]),
+                             goal=g, kind=kind, tag=probe))
+
+        for _ in range(n):
+            for probe in Q_PROBES:
+                u = rng.uniform
+                # through the mouth onto the front face: the end of step `steps` lands at the probe
+                speed, steps = u(5.5, 8.0), int(rng.integers(3, 5))
+                x = front - gs * (rho + probe) - gs * _q_travel(speed, steps)
+                add("face", (x, cy + u(-0.8, 0.8)), (gs * speed, 0.0), probe)
+                # from behind, outside the rink, onto an outer corner of the box (Euclidean distance to the vertex)
+                speed, steps, phi, b = u(5.5, 8.0), int(rng.integers(3, 5)), u(np.pi / 6, np.pi / 3), u(-0.05, 0.05)
+                sy = float(rng.choice([-1, 1]))  # the corner at cy + sy * half; the puck comes from beyond it
+                d = np.array([-gs * np.cos(phi), -sy * np.sin(phi)])  # direction of travel
+                perp = np.array([-d[1], d[0]])
+                corner = np.array([back, cy + sy * P.GOAL_HALF[1]])
+                lam = -np.sqrt((rho + probe) ** 2 - b * b) - _q_travel(speed, steps)
+                add("corner", corner + b * perp + lam * d, speed * d, probe)
+                # along the back face, a probe's depth inside (scores once past the corner) or outside (never scores)
+                speed = u(7.0, 9.0)
+                add("along", (back + gs * (rho + probe), cy + sy * (P.GOAL_HALF[1] + u(0.5, 0.55))), (0.0, -sy * speed),
+                    probe)
+            for probe in (1e-3, 5e-3):
+                # grazing past an outer corner, the closest approach a probe short of touching: never scores
+                u = rng.uniform
+                # (3 to 13 degrees off the back face's direction: a flatter line would start inside the post)
+                speed, phi, sy = u(4.5, 8.0), u(1.35, 1.52), float(rng.choice([-1, 1]))
+                d = np.array([gs * np.cos(phi), -sy * np.sin(phi)])
+                away = np.array([gs * np.sin(phi), sy * np.cos(phi)])  # from the corner, away from the box
+                corner = np.array([back, cy + sy * P.GOAL_HALF[1]])
+                add("graze", corner + (rho + probe) * away - u(0.5, 0.6) * d, speed * d, probe)
+            # Box2D has no time of impact for a sensor: a puck that no end-of-step state shows inside must not score.
+            # Above 25 m/s the env damps the puck by 1 / 1.2 a step, so 70-80 m/s at the start are 58-67 m/s (1.17 to
+            # 1.33 a step) in flight, against the 0.31 + 0.79 a centre must skip.
+            speed = rng.uniform(70.0, 80.0)
+            add("tunnel", (front - gs * (rho + 0.31), cy + rng.uniform(-0.8, 0.8)), (gs * speed, 0.0), 0.3)
+    return rows
+
+
+# ---------------------------------------------------------------------------------------------------- measurement
+def _cone_coefficients(J, n1, n2, mu):
+    """J = alpha r1 + beta r2 with r1 / r2 the outer rays of the cone spanned by the friction cones about n1 and n2
+    (n1 -> n2 counter-clockwise or equal): both coefficients are >= 0 exactly when J lies in the cone."""
+    phi = np.arctan(mu)
+    if n1[0] * n2[1] - n1[1] * n2[0] < 0:
+        n1, n2 = n2, n1
+    rot = lambda v, a: np.array([np.cos(a) * v[0] - np.sin(a) * v[1], np.sin(a) * v[0] + np.cos(a) * v[1]])  # noqa: E731
+    return np.linalg.solve(np.stack([rot(n1, -phi), rot(n2, phi)], 1), J)
+
+
+def measure(batch, S, D, A):
+    """S[K+1,N,18] raw states, D[K,N,13] debug rows, A[K+1,N,5] aux rows before / after each step."""
+    S, D, A = np.asarray(S, np.float64), np.asarray(D, np.float64), np.asarray(A)
+    ff = np.stack([P.free_flight(S[k], D[k]) for k in range(K)])
+    free = np.stack([P.deviation(S[k + 1], ff[k]) for k in range(K)]) <= TOL_AF["A_dev"]
+    pre = [P.presolve(S[k], D[k]) for k in range(K)]
+    out = _measure_gh(batch, S, free, pre)
+    out.update(_measure_s(batch, S, pre))
+    out.update(_measure_p(batch, S))
+    out.update(_measure_q(batch, S, A))
+    return out
+
+
+def _measure_gh(batch, S, free, pre):
+    """G, H: the first step that is not free flight is the first contact step."""
+    fam, out = batch.family, {}
+    acc = {f: dict(approach=-np.inf, push=-np.inf, cone=-np.inf, energy=-np.inf, cp_out=-np.inf, cp_raw=-np.inf,
+                   min_jn=np.inf) for f in ("G", "H")}
+    gh_log = {}  # arena -> (family, step, kind, arrived, worst approach, cone excess): names the scene in a failure
+    counts = dict(G_steps=0, G_ambiguous=0, G_cp=0, G_near_cone=0, H_corner_both=0, H_goal=0, H_post=0, H_steps=0,
+                  H_ambiguous=0, H_near_cone=0, G_arrivals=0, H_arrivals=0, G_low_jn=0, H_low_jn=0)
+    for who in (0, 1):
+        for wall in ("top", "bottom"):
+            counts["G%d_%s_one" % (who + 1, wall)] = counts["G%d_%s_two" % (who + 1, wall)] = 0
+    for i in np.nonzero(np.isin(fam, ("G1", "G2", "H")))[0]:
+        ks = np.nonzero(~free[:, i])[0]
+        if not len(ks):
+            continue
+        k, who, f = int(ks[0]), int(batch.who[i]), fam[i][0]
+        a = acc[f]
+        s0, s1 = S[k][i:i + 1], S[k + 1][i:i + 1]
+        vs, ws = pre[k][0][i:i + 1], pre[k][1][i:i + 1]
+        (verts, com0), (verts1, com1) = P.racket_world(s0, who), P.racket_world(s1, who)
+        J, _ = P.racket_impulse(who, vs, ws, s1)
+        J = J[0]
+        counts[f + "_steps"] += 1
+        ambiguous, touching, arrived = False, [], False
+        # Continuous collision: a vertex that was not touching reaches the face before the step ends, and is stopped
+        # at its time of impact with an impulse of its own.  Laws 1 and 3 are about the start-of-step manifold and do
+        # not describe such a step.  It shows in the positions: without an event the centre of mass moves by
+        # dt v' plus the position solver's push-out, which points out of every face; with one it has moved part of
+        # the step with the velocity from before the event, which pointed further into the face than v' does.
+        drift = (com1 - com0 - P.DT * P.bodies(s1)[2][:, who])[0]
+        for q, n, lo, hi in batch.faces[i]:
+            n = np.asarray(n, np.float64)
+            tau, eta = P.face_coordinates(verts[0], q, n)
+            on = (tau > lo - FACE_MARGIN) & (tau < hi + FACE_MARGIN)
+            sure = (eta < 2 * P.POLY_RADIUS - ETA_MARGIN) & (tau > lo + FACE_MARGIN) & (tau < hi - FACE_MARGIN)
+            maybe = on & (eta < 2 * P.POLY_RADIUS + ETA_MARGIN)
+            ambiguous |= bool((maybe & ~sure).any())
+            touching.append((n, sure, maybe, tau))
+            arrived |= bool(drift @ n < -DRIFT_MARGIN)
+            arrived |= len(batch.faces[i]) == 1 and bool(abs(drift[0] * n[1] - drift[1] * n[0]) > DRIFT_MARGIN)
+            arrived |= bool((P.face_coordinates(verts1[0], q, n)[1][on & ~maybe] < 2 * P.POLY_RADIUS + ETA_MARGIN).any())
+        counts[f + "_arrivals"] += arrived
+        approach = -np.inf
+        for n, sure, _, _ in touching:
+            if sure.any():  # 1. non-approach: restitution 0, so no touching vertex still moves into its face
+                approach = max(approach, float(-(P.point_velocity(who, s0, s1, verts[:, sure])[0] @ n).min()))
+        if not arrived:
+            a["approach"] = max(a["approach"], approach)
+        counts[f + "_ambiguous"] += ambiguous
+        faces = [t for t in touching if t[2].any()]
+        if not faces:
+            continue
+        # 2. push only, inside the cone spanned by the touching faces' friction cones
+        n1, n2 = faces[0][0], faces[-1][0]
+        mu = float(np.sqrt(0.1 * 1.0))
+        co = _cone_coefficients(J, n1, n2, mu)
+        a["cone"] = max(a["cone"], float(-co.min() / P.M[who]))
+        gh_log[int(i)] = (f, k, str(batch.kind[i]), bool(arrived), approach, float(-co.min() / P.M[who]))
+        v1, w1 = P.bodies(s1)[2:]
+        a["energy"] = max(a["energy"], float(P.kinetic_energy(v1, w1)[0] / P.kinetic_energy(vs, ws)[0] - 1))
+        if len(batch.faces[i]) == 2:
+            counts["H_corner_both"] += all(t[1].any() for t in touching)
+            a["push"] = max(a["push"], float(-(J @ (n1 + n2)) / P.M[who]))
+            continue  # 3. does not apply: two faces' impulses have no common contact plane
+        n, sure, maybe, tau = faces[0]
+        t = np.array([n[1], -n[0]])
+        jn, jt = float(J @ n), float(J @ t)
+        a["push"] = max(a["push"], -jn / P.M[who])
+        near_cone = abs(jt) >= NEAR_CONE * mu * jn and jn > 0
+        counts[f + "_near_cone"] += near_cone
+        if f == "H" and not ambiguous and sure.any():
+            counts["H_" + str(batch.kind[i])] += 1
+        if f == "G" and not ambiguous:
+            counts["%s_%s_%s" % (fam[i], "top" if batch.tag[i] > 0 else "bottom", ("one", "two")[int(sure.sum() > 1)])] += 1
+        # 3. centre of pressure: within the extent of the vertices that can be manifold points.  Not where
+        # another vertex arrived before the step ended (above).
+        counts[f + "_low_jn"] += jn < G3_MIN_JN
+        if jn >= G3_MIN_JN and not arrived:
+            q = batch.faces[i][0][0]
+            cp, bar, _, _ = P.centre_of_pressure(who, s0, s1, vs, ws, q, n)
+            lo, hi = tau[maybe].min(), tau[maybe].max()
+            a["cp_out"] = max(a["cp_out"], float(max(lo - cp[0] - bar[0], cp[0] - hi - bar[0])))
+            a["cp_raw"] = max(a["cp_raw"], float(max(lo - cp[0], cp[0] - hi)))
+            a["min_jn"] = min(a["min_jn"], jn)
+            counts["G_cp"] += f == "G"
+    for f, a in acc.items():
+        for key, v in a.items():
+            out["%s_%s" % (f, key)] = float(v)
+    out.update(counts, GH_log=gh_log)
+    out["G_scenes"] = int(np.isin(fam, ("G1", "G2")).sum())
+    out["H_scenes"] = int((fam == "H").sum())
+    return out
+
+
+def _measure_s(batch, S, pre):
+    """S: the first step, while float64 geometry says the puck is trapped (both gaps inside the skins by ETA_MARGIN,
+    its centre S_SPAN_MARGIN inside the ends of the racket's face): after the step the puck moves neither into the
+    wall nor into the face.  Returns the worst approach speed of either contact."""
+    worst, trapped, log = -np.inf, 0, {}
+    for i in np.nonzero(batch.family == "S")[0]:
+        who, wall = int(batch.who[i]), batch.tag[i]
+        s0, s1 = S[0][i:i + 1], S[1][i:i + 1]
+        o0, a0, _, _ = P.bodies(s0)
+        _, _, v1, w1 = P.bodies(s1)
+        sgn = 1.0 if who == 0 else -1.0
+        nf = sgn * np.array([np.cos(a0[0, who]), np.sin(a0[0, who])])
+        rel = o0[0, 2] - o0[0, who]
+        gap_r = rel @ nf - 0.1 - P.R
+        along = rel[0] * -nf[1] + rel[1] * nf[0]
+        gap_w = wall * ((P.Y_TOP if wall > 0 else P.Y_BOT) - o0[0, 2, 1]) - P.R
+        if not (max(gap_r, gap_w) < P.POLY_RADIUS - ETA_MARGIN and abs(along) < 0.4 - S_SPAN_MARGIN):
+            continue
+        trapped += 1
+        into_wall = wall * v1[0, 2, 1]
+        foot = (o0[0, 2] - (gap_r + P.R) * nf)[None, None]
+        into_face = -float((v1[0, 2] - P.point_velocity(who, s0, s1, foot)[0, 0]) @ nf)
+        log[int(i)] = (float(into_wall), into_face)
+        worst = max(worst, float(into_wall), into_face)
+    return dict(S_approach=float(worst), S_trapped=trapped, S_scenes=int((batch.family == "S").sum()), S_log=log)
+
+
+def _measure_p(batch, S):
+    """P: the first two steps."""
+    fam, out = batch.family, {}
+    dev, lin, ang, still, off_axis, seen = 0.0, 0.0, 0.0, 0.0, 0.0, set()
+    p_log, moved = {}, {}
+    for i in np.nonzero(fam == "P")[0]:
+        who = int(batch.who[i])
+        for k in (0, 1):
+            s0, s1 = S[k][i:i + 1], S[k + 1][i:i + 1]
+            o0, a0, _, _ = P.bodies(s0)
+            o1, a1, v1, w1 = P.bodies(s1)
+            still = max(still, float(np.abs(v1).max()), float(np.abs(w1).max()))
+            pair = (0, 1) if batch.kind[i] == "rackets" else (who, 2)
+            c0 = np.stack([P.racket_world(s0, j)[1][0] if j < 2 else o0[0, 2] for j in pair])
+            c1 = np.stack([P.racket_world(s1, j)[1][0] if j < 2 else o1[0, 2] for j in pair])
+            m = P.M[list(pair)][:, None]
+            dc = c1 - c0
+            lin = max(lin, float(np.abs((m * dc).sum(0)).max()))
+            if batch.kind[i] == "axis":
+                sep0, sep1 = p_separation(s0, who)[0], p_separation(s1, who)[0]
+                want = P.position_recurrence(sep0)
+                dev = max(dev, abs(sep1 - want))
+                off_axis = max(off_axis, float(np.abs(dc[:, 1]).max()), abs(a1[0, who] - a0[0, who]))
+                if k == 0:
+                    seen.add((who, batch.tag[i]))
+                p_log[(who, batch.tag[i], k)] = (float(sep0), float(sep1), float(want))
+            else:
+                r = c0 - c0.mean(0)
+                da = (a1 - a0)[0, list(pair)]
+                inertia = P.I[list(pair)]
+                moved[batch.kind[i]] = moved.get(batch.kind[i], 0) + bool(np.abs(dc).max() > 1e-4)
+                num = (m[:, 0] * (r[:, 0] * dc[:, 1] - r[:, 1] * dc[:, 0]) + inertia * da).sum()
+                ang = max(ang, abs(float(num)))
+    out.update(P_recurrence=dev, P_momentum=lin, P_angular=ang, P_velocity=still, P_off_axis=off_axis, P_seen=seen,
+               P_log=p_log, P_off_moved=moved.get("off", 0), P_rackets_moved=moved.get("rackets", 0))
+    return out
+
+
+def _measure_q(batch, S, A):
+    """Q: done first becomes 1 in the step after the first one whose end state overlaps the sensor."""
+    fam, out = batch.family, {}
+    wrong, q_log = [], []
+    q_counts = {"Q%d_%s" % (g, c): 0 for g in (0, 1) for c in ("score_minus", "score_plus", "graze", "tunnel",
+                                                               "corner", "face")}
+    min_abs = np.inf
+    for i in np.nonzero(fam == "Q")[0]:
+        g = int(batch.goal[i])
+        sep = P.goal_separation(S[:, i, 12:14], g)
+        min_abs = min(min_abs, float(np.abs(sep).min()))
+        inside = np.nonzero(sep[1:] < 0)[0]  # step indices whose END state overlaps
+        want_done = np.zeros(K + 1, np.int64)
+        if len(inside):
+            want_done[int(inside[0]) + 2:] = 1  # seen by the next step's collide; aux rows are indexed by state
+        want_win = want_done * (-1 if g == 0 else 1)
+        if sep[0] < 0 or (A[:, i, 3] != want_done).any() or (A[:, i, 4] != want_win).any():
+            wrong.append((int(i), str(batch.kind[i]), float(batch.tag[i])))
+        q_log.append((str(batch.kind[i]), float(batch.tag[i]), [float(x) for x in sep], [int(x) for x in A[:, i, 3]]))
+        if len(inside) and inside[0] + 2 <= K:
+            j = int(inside[0]) + 1  # index of the deciding state
+            if -6e-3 < sep[j] < 0:
+                q_counts["Q%d_score_minus" % g] += 1
+            if 0 < sep[j - 1] < 6e-3:
+                q_counts["Q%d_score_plus" % g] += 1
+            if batch.kind[i] in ("corner", "face"):
+                q_counts["Q%d_%s" % (g, batch.kind[i])] += 1
+        elif not len(inside):
+            if batch.kind[i] in ("graze", "along") and sep.min() < 6e-3:
+                q_counts["Q%d_graze" % g] += 1
+            if batch.kind[i] == "tunnel" and (np.diff(np.sign(S[:, i, 12] - P.GOAL_CENTRE[g][0])) != 0).any():
+                q_counts["Q%d_tunnel" % g] += 1
+    out.update(Q_wrong=wrong, Q_log=q_log, Q_min_abs=min_abs, Q_scenes=int((fam == "Q").sum()), **q_counts)
+    return out
+
+
+def check(m):
+    """Every law within its tolerance, and the scenes' coverage conditions."""
+    for k, v in MIN_COUNTS.items():
+        assert m[k] >= v, (k, m[k], v)
+    # a law's own validity filter may drop at most a tenth of its family's first contact steps
+    for f in ("G", "H"):
+        assert m[f + "_steps"] >= 0.9 * m[f + "_scenes"], (f, m[f + "_steps"], m[f + "_scenes"])
+        assert m[f + "_ambiguous"] <= MAX_DROPPED * m[f + "_steps"], (f, "ambiguous vertices", m[f + "_ambiguous"])
+        assert m[f + "_arrivals"] <= MAX_DROPPED * m[f + "_steps"], (f, "arrivals", m[f + "_arrivals"])
+        worst = max((v for v in m["GH_log"].items() if v[1][0] == f and not v[1][3]), key=lambda v: v[1][4],
+                    default=None)
+        assert m[f + "_approach"] <= TOL[f + "_approach"], (f, "a touching vertex still approaches", worst)
+        assert m[f + "_push"] <= TOL[f + "_push"], (f, "the wall pulls", m[f + "_push"])
+        assert m[f + "_cone"] <= TOL[f + "_cone"], (f, "outside the friction cone", m[f + "_cone"])
+        assert m[f + "_energy"] <= TOL[f + "_energy"], (f, "kinetic energy rose", m[f + "_energy"])
+    # 3 is asserted for G alone.  H's corners have no common contact plane; on its goal-box scenes the figure is
+    # recorded (H_cp_out) but on other seeds one scene in a few hundred lies outside its own bar, by up to 2.7 mm:
+    # a continuous-collision event with an impulse so small that the push-out hides its drift
+    assert m["G_cp_out"] <= 0.0, ("G centre of pressure outside the contact patch", m["G_cp_out"])
+    assert m["G_cp"] >= (1 - MAX_DROPPED) * m["G_steps"], ("G centre of pressure asserted on", m["G_cp"], m["G_steps"])
+    print("dropped: G laws 1 / 3 (another vertex arrived mid-step) %.1f %%, G law 3 in all %.1f %%, H laws 1 / 3 %.1f %%,"
+          " G / H vertices at the margin %.1f / %.1f %%" % (
+              100 * m["G_arrivals"] / m["G_steps"], 100 - 100 * m["G_cp"] / m["G_steps"],
+              100 * m["H_arrivals"] / m["H_steps"], 100 * m["G_ambiguous"] / m["G_steps"],
+              100 * m["H_ambiguous"] / m["H_steps"]))
+    assert m["S_trapped"] >= (1 - MAX_DROPPED) * m["S_scenes"], ("S trapped first steps", m["S_trapped"])
+    assert m["S_approach"] <= TOL["S_approach"], ("S the squeezed puck still closes", m["S_approach"], m["S_log"])
+    assert m["P_seen"] == {(w, s) for w in (0, 1) for s in P_DEPTHS}, m["P_seen"]
+    assert m["P_recurrence"] <= TOL["P_recurrence"], ("P recurrence", m["P_recurrence"], m["P_log"])
+    assert m["P_velocity"] == 0.0, ("P velocities", m["P_velocity"])
+    assert m["P_momentum"] <= TOL["P_momentum"], ("P sum m dc", m["P_momentum"])
+    assert m["P_off_axis"] <= TOL["P_off_axis"], ("P rotation / y motion on the axis", m["P_off_axis"])
+    assert m["P_angular"] <= TOL["P_angular"], ("P sum m c x dc + I da", m["P_angular"])
+    assert m["Q_min_abs"] > Q_BAND, m["Q_min_abs"]
+    assert not m["Q_wrong"], ("Q done / winner", m["Q_wrong"])
+
+
+def run(env, batch):
+    """(S, D, A): physics_scenes.run with the aux rows as well."""
+    return run_af(env, batch, aux=True)
