@@ -12,7 +12,9 @@ step is ONE call into the library (hk_step_host): the action and the opponent's 
 pinned staging, the step kernel runs, and the packed result (obs, obs2, done, the float64 record) comes back
 before the call returns.  The fused
 ``HockeyEnv_BasicOpponent`` opponent draws its phase from the global ``np.random`` exactly like the
-reference's ``BasicOpponent`` (:785, :796), so seeded reference scripts reproduce.  ``render`` is out of scope.
+reference's ``BasicOpponent`` (:785, :796), so seeded reference scripts reproduce.  ``render("rgb_array")`` returns
+the reference's (480, 600, 3) uint8 frame, drawn on the GPU by the written coverage law of csrc/hk_render.h (it
+differs from pygame's pixels only within 1 px of shape edges); ``render("human")`` draws nothing: there is no window.
 """
 import ctypes
 import struct
@@ -288,7 +290,15 @@ class HockeyEnv:
             action_cont.append((discrete_action == 7) * 1.0)
         return action_cont
 
-    def render(self, mode="human"):  # pragma: no cover - UI is out of scope
+    def render(self, mode="human"):
+        """hockey_env.py:697-744.  "rgb_array": the (480, 600, 3) uint8 frame of the current state, drawn on the GPU
+        (VecHockeyEnv.render).  "human": there is no window here; warns and returns None.  None: warns, as the
+        reference does (:698-702)."""
+        if mode is None:
+            warnings.warn("the render method needs a rendering mode")
+            return None
+        if mode == "rgb_array":
+            return self._vec.render()[0].cpu().numpy()
         warnings.warn("hockey_amd: render() is not part of the accelerated hot path; nothing is drawn")
         return None
 

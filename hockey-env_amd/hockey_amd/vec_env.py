@@ -11,6 +11,7 @@ onto the reference's per-env call, vectorised over a leading arena axis and kept
   obs_agent_two()          :500              obs_agent_two()  (or step(..., with_agent_two=True))
   get_info_agent_two()/get_reward_agent_two  returned by step(..., with_agent_two=True)
   set_state(s[18])         :594              set_state(state[N,18] raw, aux[N,5])
+  render("rgb_array")      :697              render(indices) -> uint8 [m,480,600,3] (any size, or palette indices)
   BasicOpponent.act        :787              policy=('external'|'random'|'weak'|'strong') per player
   ========================================  ================================================
 
@@ -288,6 +289,15 @@ class VecHockeyEnv:
         aux = torch.zeros((self.n, N.AUX_DIM), dtype=torch.int32, device=self.device)
         N.check(self.L.hk_get_state(self._ctx, N.ptr(st), N.ptr(aux), self._stream()), "hk_get_state")
         return st, aux
+
+    def render(self, indices=None, height=480, width=600, format="rgb", out=None):
+        """HockeyEnv.render("rgb_array") (hockey_env.py:697-744) for the arenas ``indices`` (all when None), at any
+        size: a uint8 device tensor [m, height, width, 3], or [m, height, width] palette indices with
+        format="index" (hockey_amd.render).  The frames show the current state; rendering does not touch it."""
+        from .render import render_states
+
+        st, _ = self.get_state()
+        return render_states(st, indices, height, width, format, out=out)
 
     def set_state(self, state=None, aux=None, mask=None):
         st = None if state is None else torch.as_tensor(state, dtype=torch.float32, device=self.device).contiguous()
