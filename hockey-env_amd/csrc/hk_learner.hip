@@ -13,7 +13,9 @@
 //                 soft_update (:196-218) folded in;
 //   pack          re-lays the changed weights out for the MFMA operands (polyak: soft_update as its own launch).
 //   per_*         prioritized replay on per-block float64 sums: slots, importance weights, the priority write-back and
-//                 the push rule without a pass over the ring (at the end of this file).
+//                 the push rule without a pass over the ring (after the C ABI of the stages above).
+//   act           acting: the actor forward of actor_step over a bank of policies, a different one per row, the rows
+//                 grouped by policy on the device (at the end of this file).
 //
 // Every product is v_mfma_f32_16x16x4_f32: exact f32 fma chains (no reduced-precision path on gfx950), so the
 // arithmetic is the reference's fp32 up to summation order.  Layout of a wave's activations ("Tile"): lane l holds
@@ -1316,6 +1318,154 @@ int hkl_per_update(const hkl_per_update_io *io, void *stream) {
   hipLaunchKernelGGL(hkl::per_touch_kernel, dim3((unsigned)((io->batch + 3) / 4)), dim3(256), 0, st, *io);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? HKL_OK : fail(e, "hkl_per_update");
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ actor inference
+// hkl_act: the actor forward tanh(W3 tanh(W2 tanh(W1 obs + b1) + b2) + b3) of actor_step_kernel's first third, for
+// acting: every row of a batch runs the policy its `policy` entry names out of a bank of K (self-play pools,
+// cross-play).  The layer routines stage ONE network's fragments in LDS for the 4 waves of a workgroup, so the rows
+// are first grouped by policy on the device and every workgroup takes 64 rows of one group:
+//   act_hist_kernel     counts[k] = rows of policy k: a histogram per workgroup in LDS, then one global atomic per
+//                       (workgroup, occupied k);
+//   act_scan_kernel     offsets = the exclusive scan of the K counts (offsets[K] = the rows that act), counts := 0;
+//   act_scatter_kernel  order[offsets[k] + ..] = the rows of policy k: a workgroup reserves its rows' range with one
+//                       atomic per occupied k on counts (now the groups' cursors) and ranks them in LDS;
+//   act_kernel          workgroup b walks the offsets to its (policy, 64-row chunk) and runs gemm_in / gemm256 /
+//                       gemm_out on the gathered rows.
+// The order of the rows inside a group depends on the atomics' timing; the results do not: in a 16x16x4 MFMA a
+// sample's output column is a function of its own B column alone, and every sample's k-steps run in the same order,
+// so a row's four outputs are the same bits wherever it sits and whoever its tile-mates are.
+namespace hkl {
+
+constexpr int kActW1 = 0, kActB1 = kActW1 + H * 18, kActW2 = kActB1 + H, kActB2 = kActW2 + H * H, kActW3 = kActB2 + H,
+              kActB3 = kActW3 + 4 * H;
+static_assert(kActB3 + 4 == HKL_ACT_PARAM_FLOATS, "parameter block (include/hockey_learner.h)");
+static_assert(HKL_ACT_PARAM_FLOATS % 4 == 0 && HKL_PACK_FLOATS % 4 == 0, "bank slots keep 16-byte alignment");
+
+// a row's policy, or -1 for a row that does not act (any id outside [0, K) is treated as -1: no lane indexes the
+// tables with it)
+__device__ __forceinline__ int act_policy(const hkl_act_io &io, int i) {
+  const int k = io.policy[i];
+  return (k >= 0 && k < io.n_policies) ? k : -1;
+}
+
+__global__ void __launch_bounds__(256) act_hist_kernel(hkl_act_io io) {
+  __shared__ int h[HKL_ACT_MAX_POLICIES];
+  if (threadIdx.x < HKL_ACT_MAX_POLICIES) h[threadIdx.x] = 0;
+  __syncthreads();
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int k = i < io.n_rows ? act_policy(io, i) : -1;
+  if (k >= 0) atomicAdd(&h[k], 1);
+  __syncthreads();
+  if (threadIdx.x < io.n_policies && h[threadIdx.x]) atomicAdd(&io.counts[threadIdx.x], h[threadIdx.x]);
+}
+
+// one wave: a Kogge-Stone scan over the (at most 64) counts
+__global__ void __launch_bounds__(64) act_scan_kernel(hkl_act_io io) {
+  const int l = threadIdx.x;
+  const int c = l < io.n_policies ? io.counts[l] : 0;
+  int s = c;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int t = __shfl_up(s, d);
+    if (l >= d) s += t;
+  }
+  if (l < io.n_policies) {
+    io.offsets[l] = s - c;
+    io.counts[l] = 0;  // the scatter's cursors
+  }
+  if (l == io.n_policies - 1) io.offsets[io.n_policies] = s;
+}
+
+__global__ void __launch_bounds__(256) act_scatter_kernel(hkl_act_io io) {
+  __shared__ int h[HKL_ACT_MAX_POLICIES], base[HKL_ACT_MAX_POLICIES];
+  if (threadIdx.x < HKL_ACT_MAX_POLICIES) h[threadIdx.x] = 0;
+  __syncthreads();
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int k = i < io.n_rows ? act_policy(io, i) : -1;
+  const int rank = k >= 0 ? atomicAdd(&h[k], 1) : 0;
+  __syncthreads();
+  if (threadIdx.x < io.n_policies && h[threadIdx.x])
+    base[threadIdx.x] = io.offsets[threadIdx.x] + atomicAdd(&io.counts[threadIdx.x], h[threadIdx.x]);
+  __syncthreads();
+  if (k >= 0) io.order[base[k] + rank] = i;  // < offsets[k + 1] <= n_rows: the hist pass counted the same rows
+}
+
+__global__ void __launch_bounds__(WG, 1) act_kernel(hkl_act_io io) {
+  __shared__ f4 sfrag[2 * 16 * 64 + 64];  // two fragment buffers + the staged bias
+  // this workgroup's policy k and its rows [start, start + cnt) of the group, 64 per workgroup.  Everything up to
+  // the return depends on blockIdx and the arguments alone, so a surplus workgroup leaves as a whole before the
+  // first barrier.
+  int k = 0, start = 0, cnt = 0;
+  if (io.policy) {
+    int b = (int)blockIdx.x, lo = io.offsets[0];
+    for (k = 0; k < io.n_policies; ++k) {
+      const int hi = io.offsets[k + 1], tiles = (hi - lo + 63) >> 6;
+      if (b < tiles) {
+        start = lo + 64 * b;
+        cnt = hi - start;
+        break;
+      }
+      b -= tiles;
+      lo = hi;
+    }
+    if (k == io.n_policies) return;
+  } else {
+    start = 64 * (int)blockIdx.x;
+    cnt = io.n_rows - start;
+  }
+  if (cnt <= 0) return;  // (never taken: a tile holds at least one row)
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, j = lane & 15;
+  // a partly filled workgroup: its spare lanes recompute the group's last row of this chunk and store nothing
+  const int r = wave * 16 + j;
+  const bool live = r < cnt;
+  const int pos = start + (live ? r : cnt - 1);
+  const int64_t row = io.policy ? io.order[pos] : pos;
+  const float *par = io.params + (int64_t)k * HKL_ACT_PARAM_FLOATS;
+  const Net an{par + kActW1, par + kActB1, par + kActW2, par + kActB2, par + kActW3, par + kActB3,
+               io.packs + (int64_t)k * HKL_PACK_FLOATS, 18, 4};
+  float x[S1];
+  input_frags(io.obs + row * io.obs_ld, z4(), false, x, q);
+  Tile h1, h2;
+  gemm_in(an.f1(), x, h1, lane, sfrag);
+  gemm256(an.fp(), h1, an.b1, h2, lane, sfrag);
+  const f4 pre = gemm_out(an.fo(), h2, an.b2, an.b3, 4, lane, sfrag);
+  // the sample's 4 lanes hold the same outputs: lane q stores component q
+  const float a = tanh_fast(q == 0 ? pre[0] : q == 1 ? pre[1] : q == 2 ? pre[2] : pre[3]);
+  if (live) io.out[row * io.out_ld + io.out_col + q] = a;
+}
+
+}  // namespace hkl
+
+extern "C" {
+
+int hkl_act_io_size(void) { return (int)sizeof(hkl_act_io); }
+
+int hkl_act(const hkl_act_io *io, void *stream) {
+  if (!io || io->n_policies < 1 || io->n_policies > HKL_ACT_MAX_POLICIES || io->n_rows < 0 || io->obs_ld < 18 ||
+      io->out_col < 0 || io->out_ld < (int64_t)io->out_col + 4)
+    return HKL_E_INVALID;
+  if (!io->params || !io->packs || !io->obs || !io->out) return HKL_E_INVALID;
+  if (io->policy && (!io->order || !io->counts || !io->offsets)) return HKL_E_INVALID;
+  if (io->n_rows == 0) return HKL_OK;
+  const hipStream_t st = (hipStream_t)stream;
+  const unsigned tiles = (unsigned)((io->n_rows + 63) / 64);
+  if (io->policy) {
+    const unsigned blocks = (unsigned)((io->n_rows + 255) / 256);
+    const hipError_t m = hipMemsetAsync(io->counts, 0, sizeof(int32_t) * (HKL_ACT_MAX_POLICIES + 1), st);
+    if (m != hipSuccess) return fail(m, "hkl_act");
+    hipLaunchKernelGGL(act_hist_kernel, dim3(blocks), dim3(256), 0, st, *io);
+    hipLaunchKernelGGL(act_scan_kernel, dim3(1), dim3(64), 0, st, *io);
+    hipLaunchKernelGGL(act_scatter_kernel, dim3(blocks), dim3(256), 0, st, *io);
+    // sum_k ceil(count_k / 64) <= n_rows / 64 + K tiles, known only on the device: the surplus workgroups return
+    hipLaunchKernelGGL(act_kernel, dim3(tiles + (unsigned)io->n_policies), dim3(WG), 0, st, *io);
+  } else {
+    hipLaunchKernelGGL(act_kernel, dim3(tiles), dim3(WG), 0, st, *io);
+  }
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? HKL_OK : fail(e, "hkl_act");
 }
 
 }  // extern "C"

@@ -130,6 +130,92 @@ def evaluate(policy, episodes=100, seed=42, weak_opponent=False, mode=Mode.NORMA
     return out
 
 
+def tournament_pairs(n_actors, games, include_bots=True):
+    """The tournament's pairing table: int arrays (p1, p2, game), one entry per arena.  Arena
+    a = (i * cols + j) * games + g plays actor i as player 1 in game g against column j: actor j for j < K, the weak
+    fused bot for j = K (p2 = -1) and the strong one for j = K + 1 (p2 = -2); cols = K + 2 with the bots, else K."""
+    k, games = int(n_actors), int(games)
+    cols = k + 2 if include_bots else k
+    a = np.arange(k * cols * games)
+    j = (a // games) % cols
+    p2 = np.where(j < k, j, k - 1 - j)
+    return (a // (cols * games)).astype(np.int32), p2.astype(np.int32), (a % games).astype(np.int32)
+
+
+def tournament_fold(winner, length, n_actors, games, include_bots=True):
+    """Fold per-arena winners (+1 player 1 / 0 draw / -1 player 2) and episode lengths, in tournament_pairs' arena
+    order, into [K][cols] matrices: win / draw / loss rates of the row actor as player 1, mean length, and
+    score = win + 0.5 draw."""
+    k, games = int(n_actors), int(games)
+    cols = k + 2 if include_bots else k
+    w = np.asarray(winner).reshape(k, cols, games)
+    out = {"win": (w == 1).mean(2), "draw": (w == 0).mean(2), "loss": (w == -1).mean(2),
+           "mean_length": np.asarray(length, np.float64).reshape(k, cols, games).mean(2)}
+    out["score"] = out["win"] + 0.5 * out["draw"]
+    return out
+
+
+@torch.no_grad()
+def tournament(actors, games=20, seed=42, include_bots=True, backend="auto", per_game=False, mode=Mode.NORMAL,
+               device="cuda:0", on_step=None):
+    """Cross-play: every ordered pair of ``actors`` (K Actor modules or state dicts; actor i as player 1 against
+    actor j as player 2, i == j included) plays ``games`` games, all K * cols * games arenas stepping together in
+    one VecHockeyEnv batch.  With ``include_bots`` two more opponent columns play the weak (column K) and the strong
+    (column K + 1) fused BasicOpponent through the per-arena ``policy2`` override.  The step ABI has a per-arena
+    policy id for player 2 only, so the bots appear as columns (opponents), never as rows.
+
+    Game g of every pair starts from the same placement, ``reset_params(games, seed)`` (evaluate's placements), and
+    the bots' phases start uniform on [0, 2 pi) from ``default_rng(seed)`` as in ``evaluate``.  Each step makes two
+    ``PolicyBank.act`` calls (obs -> actions[:, 0:4], obs2 -> actions[:, 4:8]; ``backend``: PolicyBank.act's).
+
+    Returns a dict of [K][cols] float arrays ``win`` / ``draw`` / ``loss`` (of the row actor), ``mean_length`` and
+    ``score`` = win + 0.5 draw; ``per_game`` adds ``winner`` [K][cols][games] int8.  on_step(obs, obs2, actions)
+    sees every step's inputs and the actions played (test hook)."""
+    from .policy_bank import PolicyBank
+    from .vec_env import VecHockeyEnv, _POLICIES
+
+    k, games = len(actors), int(games)
+    p1, p2, g = tournament_pairs(k, games, include_bots)
+    n = len(p1)
+    dev = torch.device(device)
+    bank = PolicyBank(k, dev)
+    for a in actors:
+        bank.add(a)
+    env = VecHockeyEnv(n, keep_mode=True, mode=mode, device=dev, policies=("external", "external"), auto_reset=False,
+                       seed=seed)
+    params, max_t, _ = reset_params(games, seed, mode)
+    env.reset_params(params[g])
+    env.opponent_phase(np.random.default_rng(seed).uniform(0, 2 * np.pi, (n, 3)), rows=3)
+    ids = np.where(p2 >= 0, _POLICIES["external"], np.where(p2 == -1, _POLICIES["weak"], _POLICIES["strong"]))
+    policy2 = torch.as_tensor(ids.astype(np.uint8), device=dev)
+    pol1 = torch.as_tensor(p1, device=dev)
+    pol2 = torch.as_tensor(np.maximum(p2, -1), device=dev)
+    obs, obs2 = (t.clone() for t in env.observe())
+    length = torch.zeros(n, dtype=torch.int64, device=dev)
+    winner = torch.zeros(n, dtype=torch.float32, device=dev)
+    live = torch.ones(n, dtype=torch.bool, device=dev)
+    act = torch.zeros((n, 8), dtype=torch.float32, device=dev)
+    for _ in range(max_t + 1):
+        bank.act(obs, pol1, out=act, out_col=0, backend=backend)
+        bank.act(obs2, pol2, out=act, out_col=4, backend=backend)
+        if on_step is not None:
+            on_step(obs, obs2, act)
+        res = env.step(act, with_agent_two=True, policy2=policy2)
+        length += live.long()
+        d = res.done.bool()
+        winner = torch.where(live & d, res.info[:, 0], winner)
+        live &= ~d
+        obs, obs2 = res.obs, res.obs2
+        if not bool(live.any()):
+            break
+    env.close()
+    w = winner.cpu().numpy().astype(np.int8)
+    out = tournament_fold(w, length.cpu().numpy(), k, games, include_bots)
+    if per_game:
+        out["winner"] = w.reshape(k, -1, games)
+    return out
+
+
 # Hockey-Env.ipynb:940-2154 (cells 51-57): 1000 strong-vs-strong BasicOpponent games, unseeded resets on one
 # reused env, up to 500 steps with a break at done.  Recorded: 150 911 steps, winners +1/0/-1 = 319/368/313,
 # sum of rewards -4360.24 (agent 1) / -4367.87 (agent 2), and the per-feature mean of every step's obs.

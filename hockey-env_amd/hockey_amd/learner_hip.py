@@ -14,6 +14,9 @@ learner's own (Adam moments in fp32 device buffers): ``agent.opt_critic`` / ``op
 On a ``hockey_amd.td3.DevicePrioritizedRing`` the prioritized slots, importance weights and the priority write-back are
 the hkl_per_* kernels (per-block float64 sums; the slots come from the Philox stream under rng="device").
 
+``ActIO`` / ``hkl_act`` (actor inference over a bank of policies) is bound here and driven by
+``hockey_amd.policy_bank.PolicyBank``.
+
 Every call is asynchronous on torch's current stream and graph-capturable (fixed buffers, device step counters).
 There is no CPU path: construction fails loudly without the library or a GPU.
 """
@@ -30,6 +33,8 @@ PACK_FLOATS = 16 * 64 * 8 + 2 * 16 * 16 * 64 * 4 + 16 * 64 * 4 + 256 * 4
 MAX_SEG = 12
 CHUNK = 256  # batch granularity (include/hockey_learner.h)
 XP = 32
+ACT_MAX_POLICIES = 64  # HKL_ACT_MAX_POLICIES
+ACT_PARAM_FLOATS = 256 * 18 + 256 + 256 * 256 + 256 + 4 * 256 + 4  # HKL_ACT_PARAM_FLOATS: one bank slot's weights
 
 vp = ctypes.c_void_p
 
@@ -92,10 +97,17 @@ class PerUpdateIO(ctypes.Structure):
     _fields_ = [("per", Per), ("batch", ctypes.c_int64), ("idx", vp), ("td", vp)]
 
 
+class ActIO(ctypes.Structure):
+    """hkl_act_io: actor inference over a bank of policies (hockey_amd.policy_bank)."""
+    _fields_ = [("n_policies", ctypes.c_int32), ("n_rows", ctypes.c_int32), ("params", vp), ("packs", vp),
+                ("obs", vp), ("obs_ld", ctypes.c_int64), ("policy", vp), ("out", vp), ("out_ld", ctypes.c_int64),
+                ("out_col", ctypes.c_int32), ("order", vp), ("counts", vp), ("offsets", vp)]
+
+
 EXPORTS = ["hkl_last_error", "hkl_pack_floats", "hkl_pack", "hkl_critic_step", "hkl_actor_step", "hkl_wgrad",
            "hkl_wgrad_pair",
            "hkl_adam", "hkl_polyak", "hkl_tanh_probe", "hkl_sample", "hkl_per_block", "hkl_per_refresh",
-           "hkl_per_push", "hkl_per_sample", "hkl_per_weights", "hkl_per_update"]
+           "hkl_per_push", "hkl_per_sample", "hkl_per_weights", "hkl_per_update", "hkl_act", "hkl_act_io_size"]
 
 
 def tanh_probe(x):
@@ -132,8 +144,11 @@ def lib():
         L.hkl_per_sample.argtypes = [ctypes.POINTER(PerSampleIO), vp]
         L.hkl_per_weights.argtypes = [ctypes.POINTER(PerSampleIO), vp]
         L.hkl_per_update.argtypes = [ctypes.POINTER(PerUpdateIO), vp]
+        L.hkl_act.argtypes = [ctypes.POINTER(ActIO), vp]
         if L.hkl_pack_floats() != PACK_FLOATS:
             raise _native.HockeyNativeError("libhockey_learner.so pack size differs from hockey_amd.learner_hip")
+        if L.hkl_act_io_size() != ctypes.sizeof(ActIO):
+            raise _native.HockeyNativeError("libhockey_learner.so hkl_act_io differs from hockey_amd.learner_hip")
         _lib = L
     return _lib
 

@@ -17,11 +17,21 @@ Batched form of the reference's opponent machinery, device-resident and free of 
   reference's manager holds one ``BasicOpponent`` of each kind).
 
 Batched differences (by design, documented): the draws come from a torch generator on the device instead of
-the process-global ``np.random``; the snapshot is sampled once per step for all arenas (the reference samples
-one per step for its single env); ``register_outcome`` counts the done steps of self-play arenas against the
-snapshot they faced (the reference charges the last sampled snapshot for every done step of any opponent),
-tallied per step on the device and folded into the scores step by step at the end of the round (within one
-step, the non-win outcomes are applied before the wins; clipping follows every outcome as in the reference).
+the process-global ``np.random``; under ``sampling="step"`` (the default) the snapshot is sampled once per step
+for all arenas (the reference samples one per step for its single env); ``register_outcome`` counts the done
+steps of self-play arenas against the snapshot they faced (the reference charges the last sampled snapshot for
+every done step of any opponent), tallied per step on the device and folded into the scores step by step at the
+end of the round (within one step, the non-win outcomes are applied before the wins; clipping follows every
+outcome as in the reference).
+
+``sampling="arena"`` removes the snapshot difference: every self-play arena draws its OWN snapshot at every step,
+score-weighted (``torch.multinomial`` on the mix's device generator), as the reference does for every env-step of
+its single env (opponent_manager.py:62-91, self_play.py).  The pool mirrors its snapshots into a
+``hockey_amd.policy_bank.PolicyBank`` and ONE ``PolicyBank.act`` call (``hkl_act`` on the GPU: rows grouped by
+snapshot on the device) writes the self-play arenas' actions into ``actions[:, 4:8]``; there is no forward per
+pool member and no mask multiply.  Each done step is charged to the snapshot that arena faced at that step, as a
+per-step [pool][2] scatter-add on the device; ``end_round`` folds the steps in order (the snapshots' scores do
+not depend on each other, so the order across snapshots within a step is immaterial).
 """
 import copy
 import math
@@ -46,10 +56,13 @@ SCORE_MIN, SCORE_MAX, SCORE_LOSS, SCORE_WIN = 0.1, 10.0, 1.2, 0.95
 class SelfPlayPool:
     """Frozen actor snapshots with difficulty scores (rl/training/self_play.py)."""
 
-    def __init__(self, interval=100, pool_size=40, seed=0):
+    def __init__(self, interval=100, pool_size=40, seed=0, bank=None):
+        """bank: a PolicyBank with at least ``pool_size`` + 1 slots that mirrors the snapshots (``slots[i]`` is the
+        bank slot of ``pool[i]``; a dropped snapshot's slot is freed)."""
         self.interval, self.pool_size = int(interval), int(pool_size)
         self.episode_counter = 0
         self.pool, self.scores = [], []
+        self.bank, self.slots = bank, []
         self.rng = np.random.default_rng(seed)
 
     def step(self, actor, episodes=1):
@@ -66,9 +79,13 @@ class SelfPlayPool:
             p.requires_grad_(False)
         self.pool.append(snap)
         self.scores.append(1.0)
+        if self.bank is not None:
+            self.slots.append(self.bank.add(snap))
         if len(self.pool) > self.pool_size:
             self.pool.pop(0)
             self.scores.pop(0)
+            if self.bank is not None:
+                self.bank.free(self.slots.pop(0))
 
     def update_difficulty(self, idx, wins, others):
         """One step's outcomes against snapshot ``idx``: ``others`` outcomes that are not agent wins (x1.2 each)
@@ -97,11 +114,22 @@ class OpponentMix:
     """Per-arena, per-step opponent selection for player 2 (rl/training/opponent_manager.py)."""
 
     def __init__(self, n_arenas, curriculum="stage3", use_self_play=True, self_play_interval=100, pool_size=40,
-                 device="cuda:0", seed=0):
+                 device="cuda:0", seed=0, sampling="step", backend="auto"):
+        """sampling: "step" -- one snapshot per step for all self-play arenas; "arena" -- one per arena and step,
+        through a PolicyBank (module docstring; ``backend`` is its ``act`` backend)."""
+        if sampling not in ("step", "arena"):
+            raise ValueError("sampling must be 'step' or 'arena'")
         self.n = int(n_arenas)
         self.device = torch.device(device)
+        self.sampling, self.backend = sampling, backend
         self.table = CURRICULA[curriculum] if isinstance(curriculum, str) else [tuple(r) for r in curriculum]
-        self.pool = SelfPlayPool(self_play_interval, pool_size, seed) if use_self_play else None
+        self.bank = None
+        if use_self_play and sampling == "arena":
+            from .policy_bank import PolicyBank
+
+            # one slot more than the pool keeps: a new snapshot is added before the oldest is dropped
+            self.bank = PolicyBank(int(pool_size) + 1, self.device)
+        self.pool = SelfPlayPool(self_play_interval, pool_size, seed, self.bank) if use_self_play else None
         self.gen = torch.Generator(device=self.device)
         self.gen.manual_seed(int(seed) + 0x5EED)
         self.p_strong, self.p_weak, self.p_self = 0.0, 1.0, 0.0
@@ -119,11 +147,57 @@ class OpponentMix:
 
     def reset_stats(self):
         self._counts = torch.zeros(3, dtype=torch.int64, device=self.device)  # strong, weak, self-play
-        self._outcomes = []  # per step: device tensor [snapshot index, wins, others]
+        self._outcomes = []  # per step: device tensor [snapshot index, wins, others] ("arena": [pool][wins, others])
+        if self.bank is not None:  # arena-steps each snapshot (by pool index) was faced in this round
+            self._snap_counts = torch.zeros(self.pool.pool_size, dtype=torch.int64, device=self.device)
+        self._snap = None
 
-    def select(self, obs2):
+    def _pool_tensors(self):
+        """The pool's scores and bank slots on the device, rebuilt when either changed on the host."""
+        key = (tuple(self.pool.scores), tuple(self.pool.slots))
+        if getattr(self, "_pool_key", None) != key:
+            self._pool_key = key
+            self._scores_t = torch.tensor(self.pool.scores, dtype=torch.float32, device=self.device)
+            self._slots_t = torch.tensor(self.pool.slots, dtype=torch.int32, device=self.device)
+        return self._scores_t, self._slots_t
+
+    def _select_arena(self, obs2, out):
+        """sampling="arena": (policy2 [N] uint8, actions [N,8] or None, bank slot per arena [N] int32 or None).
+        The self-play arenas' player-2 actions are written into ``out[:, 4:8]`` (``out``: the caller's [N,8] action
+        buffer, or one kept here); every other float of it is left alone."""
+        n, dev = self.n, self.device
+        have = len(self.pool) > 0
+        u_sp = torch.rand(n, device=dev, generator=self.gen)
+        u_bot = torch.rand(n, device=dev, generator=self.gen)
+        sp = (u_sp < self.p_self) if have else torch.zeros(n, dtype=torch.bool, device=dev)
+        strong = ~sp & (u_bot < self.p_strong)
+        weak = ~sp & ~strong
+        p2 = self._policy2
+        p2.fill_(N.POLICY_BASIC_WEAK)
+        p2.masked_fill_(strong, N.POLICY_BASIC_STRONG)
+        p2.masked_fill_(sp, N.POLICY_EXTERNAL)
+        self._counts += torch.stack([strong.sum(), weak.sum(), sp.sum()])
+        self._sp_mask, self._snap = sp, None
+        if not have:
+            return p2, None, None
+        scores, slots = self._pool_tensors()
+        snap = torch.multinomial(scores, n, replacement=True, generator=self.gen)  # pool index per arena
+        policy = torch.where(sp, slots[snap], torch.full((), -1, dtype=torch.int32, device=dev))
+        if out is None:
+            if getattr(self, "_act8", None) is None:
+                self._act8 = torch.zeros((n, 8), dtype=torch.float32, device=dev)
+            out = self._act8
+        self.bank.act(obs2, policy, out=out, out_col=4, backend=self.backend)
+        self._snap = snap
+        self._snap_counts.scatter_add_(0, snap, sp.to(torch.int64))
+        return p2, out, policy
+
+    def select(self, obs2, out=None):
         """(policy2 [N] uint8, player-2 actions [N,4] or None, snapshot index or None) for this step.
-        obs2: [N,18] agent-two observations (device)."""
+        obs2: [N,18] agent-two observations (device).  sampling="arena": see _select_arena (``out`` is used by
+        that mode only)."""
+        if self.sampling == "arena" and self.pool is not None:
+            return self._select_arena(obs2, out)
         n, dev = self.n, self.device
         idx = self.pool.sample() if self.pool is not None else None
         u_sp = torch.rand(n, device=dev, generator=self.gen)
@@ -148,6 +222,16 @@ class OpponentMix:
         """Done steps of this step's self-play arenas: agent win (reward > 0) or not (opponent_manager
         register_outcome -> update_difficulty).  Tallied per step on the device; end_round() applies the steps in
         order, clipping after every outcome."""
+        if self.bank is not None:
+            if self._snap is None:
+                return
+            d = (done != 0) & self._sp_mask
+            win = d & (reward > 0)
+            tally = torch.zeros((self.pool.pool_size, 2), dtype=torch.int64, device=self.device)
+            tally[:, 0].scatter_add_(0, self._snap, win.to(torch.int64))
+            tally[:, 1].scatter_add_(0, self._snap, (d & ~win).to(torch.int64))
+            self._outcomes.append(tally)
+            return
         if self._idx is None:
             return
         d = (done != 0) & self._sp_mask
@@ -159,12 +243,20 @@ class OpponentMix:
         """Fold the round's outcomes into the snapshot scores, advance the self-play episode counter (taking a
         snapshot on an interval boundary) and return the round's opponent counts."""
         counts = self._counts.cpu().tolist()
+        out = {"strong": counts[0], "weak": counts[1], "self_play": counts[2]}
         if self.pool is not None:
-            if self._outcomes:
+            if self.bank is not None:
+                out["snapshots"] = self._snap_counts[:len(self.pool)].cpu().tolist()
+                if self._outcomes:
+                    for step in torch.stack(self._outcomes).cpu().tolist():
+                        for idx, (w, o) in enumerate(step[:len(self.pool)]):
+                            if w or o:
+                                self.pool.update_difficulty(idx, w, o)
+            elif self._outcomes:
                 for idx, w, o in torch.stack(self._outcomes).cpu().tolist():
                     if idx < len(self.pool) and (w or o):
                         self.pool.update_difficulty(idx, w, o)
             if actor is not None and episodes:
                 self.pool.step(actor, episodes)
         self.reset_stats()
-        return {"strong": counts[0], "weak": counts[1], "self_play": counts[2]}
+        return out

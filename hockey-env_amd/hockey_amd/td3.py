@@ -600,7 +600,8 @@ class Learner:
 def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_per_round=None, mode=Mode.NORMAL,
           curriculum=None, use_self_play=None, self_play_interval=None, pool_size=None, reset="seeded", log=None,
           replay_capacity=None, graphs=True, eval_fn=None, learner_batch=None, timing=False, replay_ratio=None,
-          env=None, on_step=None, episode_end="max_steps", fused="auto", resume_from=None, per_sampler="torch"):
+          env=None, on_step=None, episode_end="max_steps", fused="auto", resume_from=None, per_sampler="torch",
+          self_play_sampling=None, mix=None):
     """Batched TD3 training (rl/training/train.py TD3Trainer.train).  Each round runs ``max_steps`` steps of
     ``n_arenas`` parallel episodes (no break on done), stores every transition, then performs the learner
     updates of those episodes at the replay ratio: ``ratio * n_arenas * max_steps / B`` updates of batch B =
@@ -632,7 +633,12 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
 
     per_sampler: with ``cfg.prioritized_replay``, "torch" (default) keeps PrioritizedRing's whole-ring PyTorch
     sampling and its random stream; "device" uses DevicePrioritizedRing (per-block sums, the hkl_per_* kernels; the
-    fused learner then draws the slots from its Philox stream)."""
+    fused learner then draws the slots from its Philox stream).
+
+    self_play_sampling: "step" (default, also None) draws one pool snapshot per step for all self-play arenas;
+    "arena" draws one per arena and step, played through a PolicyBank in one call (hockey_amd.opponents); the
+    round's ``stats["opponents"]`` entry then also lists the arena-steps per snapshot.  mix: a ready OpponentMix
+    for ``n_arenas`` on ``device`` to use instead of building one (a pool carried over from an earlier run)."""
     import time
     from .opponents import OpponentMix
     from .vec_env import VecHockeyEnv
@@ -652,7 +658,12 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
     if own_env:
         env = VecHockeyEnv(n_arenas, mode=mode, device=device, policies=("external", "external"), auto_reset=False,
                            seed=seed)
-    mix = OpponentMix(n_arenas, curriculum, use_self_play, self_play_interval, pool_size, device, seed)
+    if mix is None:
+        mix = OpponentMix(n_arenas, curriculum, use_self_play, self_play_interval, pool_size, device, seed,
+                          sampling=self_play_sampling or "step")
+    elif self_play_sampling is not None and mix.sampling != self_play_sampling:
+        raise ValueError(f"mix samples per {mix.sampling}, self_play_sampling asks for {self_play_sampling}")
+    per_arena = mix.sampling == "arena"
     cap = replay_capacity or max(cfg.buffer_size, n_arenas * cfg.max_steps)
     per_ring = DevicePrioritizedRing if per_sampler == "device" else PrioritizedRing
     ring = (per_ring(cap, device=device, beta=cfg.beta) if cfg.prioritized_replay
@@ -689,7 +700,11 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
         n_alive, round_steps = n_arenas, 0
         for _ in range(cfg.max_steps):
             a = agent.act(obs, count=n_alive)
-            policy2, a2, _ = mix.select(obs2)
+            if per_arena:  # the self-play arenas' actions land in act8[:, 4:8] directly
+                policy2, _, _ = mix.select(obs2, out=act8)
+                a2 = None
+            else:
+                policy2, a2, _ = mix.select(obs2)
             act8[:, :4] = a
             if a2 is not None:
                 act8[:, 4:] = a2

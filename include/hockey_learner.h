@@ -193,6 +193,36 @@ int hkl_per_update(const hkl_per_update_io *io, void *stream);
 /* y = the kernels' tanh of x (n floats; a test probe of the activation's accuracy) */
 int hkl_tanh_probe(const float *x, float *y, int64_t n, void *stream);
 
+/* ---- actor inference over a bank of policies (hockey_amd/policy_bank.py) ----
+ * A bank is n_policies <= HKL_ACT_MAX_POLICIES actors 18 -> 256 -> 256 -> 4 (tanh hidden and output) in two strided
+ * buffers: params [K][HKL_ACT_PARAM_FLOATS] = fc1.weight [256][18], fc1.bias, fc2.weight [256][256], fc2.bias,
+ * fc3.weight [4][256], fc3.bias of each slot in torch layout, and packs [K][HKL_PACK_FLOATS], slot k written by
+ * hkl_pack from a hkl_net that points into params[k] (n_in 18, n_out 4).
+ *
+ * Row i < n_rows with policy[i] = k in [0, K): out[i * out_ld + out_col .. + 4) = slot k's actor on obs[i * obs_ld ..
+ * + 18).  A row with policy[i] = -1 (or any id outside [0, K)) is not written, and no other float of out is.
+ * policy == NULL: every row runs slot 0 and nothing is grouped (order / counts / offsets may be NULL).  With policy
+ * given the rows are grouped by policy on the device in the caller's scratch: order [n_rows], counts and offsets
+ * [HKL_ACT_MAX_POLICIES + 1] each (int32; contents on entry irrelevant, overwritten).  A row's result does not depend
+ * on the other rows, their policies or its position (bit for bit).  Asynchronous on stream, graph-capturable, no
+ * host synchronisation.  HKL_E_INVALID: K outside [1, 64], n_rows < 0, obs_ld < 18, out_col < 0, out_ld < out_col + 4,
+ * a null params / packs / obs / out, or null scratch with policy given. */
+#define HKL_ACT_MAX_POLICIES 64
+#define HKL_ACT_PARAM_FLOATS (256 * 18 + 256 + 256 * 256 + 256 + 4 * 256 + 4)
+typedef struct {
+  int32_t n_policies, n_rows;
+  const float *params, *packs;
+  const float *obs;
+  int64_t obs_ld;
+  const int32_t *policy;
+  float *out;
+  int64_t out_ld;
+  int32_t out_col;
+  int32_t *order, *counts, *offsets;
+} hkl_act_io;
+int hkl_act_io_size(void);
+int hkl_act(const hkl_act_io *io, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
