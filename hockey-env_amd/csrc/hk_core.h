@@ -65,15 +65,15 @@ struct Scene {
   float friction[NP], restitution[NP];
   int manslot[NP];                                             // manifold slot or -1 (sensor)
   int edges[3][10];                                            // contact edges of each dynamic body
-  // broad-phase rejection data (performance only; results unchanged, see hk_arena.h pair_far_*)
+  // broad-phase rejection data (performance only; results unchanged, see hk_collide.h pair_far_*)
   float fx_aabb[NF][4];   // world AABB of every static fixture {minx, miny, maxx, maxy}
   float rcore[3];         // max distance from a dynamic body's COM to its core (radius-free) shape
 };
 
-// rounding margin of the polygon-pair rejection (2 x total radius, hk_arena.h pair_far_collide): contacts use
+// rounding margin of the polygon-pair rejection (2 x total radius, hk_collide.h pair_far_collide): contacts use
 // at most ~1.4 x total radius (tests/test_broadphase_bound.py), float rounding ~1e-5 m
 constexpr float kFarMargin = 0.005f;
-// margin of the exact distance rejections (hk_arena.h pair_far_toi, circle pairs of pair_far_collide): covers
+// margin of the exact distance rejections (hk_collide.h pair_far_toi, circle pairs of pair_far_collide): covers
 // the float rounding of sweep interpolation, transforms and GJK distances (~1e-5 m here), far below it
 constexpr float kToiMargin = 0.005f;
 

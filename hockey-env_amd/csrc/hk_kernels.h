@@ -56,7 +56,7 @@ static_assert(NMF == 16, "a manifold record is four 16-byte quads");
 struct DevState {
   float *f;
   int32_t *i;  // packed int words [NPW][N] (PW_*)
-  float *man;  // manifold records [NSOLID][N][NMF] (64 B per record, hk_arena.h ManRec)
+  float *man;  // manifold records [NSOLID][N][NMF] (64 B per record, hk_body.h man_rec)
   float *ws;  // large-island slot workspace [kBigC][kSlotWords][N] (hk_solver.h HbmSlots)
   double *phase;  // BasicOpponent phases [3][N]: player 1, player 2 (its policy / the strong bot under a
                   // per-arena override), player 2's weak bot under an override (hk_step_io.policy2)

@@ -8,7 +8,7 @@
 // Float operation order is the oracle's.  This file holds the slots, the contact rows and the slot files; the 180
 // velocity iterations over them (loop families, wave dispatch, exact periodic exit) are hk_velocity.h.
 #pragma once
-// (included from hk_arena.h, which provides Arena / Dyn / pick / place / MF and the SC alias)
+// (included from hk_world.h after hk_body.h, which provides Arena / Dyn / pick / place / MF and the SC alias)
 
 namespace hk {
 

@@ -9,7 +9,7 @@
 //                               one_starts, enabled mask | winner, has_puck1 | has_puck2 | max_t, time,
 //                               episode and step counters (the 12 logical words I_* live in registers)
 //   man[NSOLID][N][NMF]  float  Box2D manifold record (64 B) of every solid pair (read/written in place,
-//                               touching only; hk_arena.h man_rec)
+//                               touching only; hk_body.h man_rec)
 //   phase[3][N]          double BasicOpponent phases: player 1, player 2, player 2's weak bot under a per-arena
 //                               override (global np.random stream -> per-arena Philox)
 #pragma once

@@ -50,7 +50,8 @@ _lib = None
 
 # the files csrc/Makefile hashes into <lib>.srchash (HASHSRC = $(SRC) $(HDR) Makefile), in its order
 HASH_SOURCES = ["hk_kernels.hip", "hk_capi.cpp", "hk_host_step.cpp", "hk_core.h", "hk_geom.h", "hk_arena.h",
-                "hk_solver.h", "hk_velocity.h", "hk_step.h", "hk_kernels.h", "hk_host_step.h",
+                "hk_body.h", "hk_collide.h", "hk_world.h", "hk_game.h", "hk_solver.h", "hk_velocity.h", "hk_step.h",
+                "hk_kernels.h", "hk_host_step.h",
                 "hk_scene_data.inc", "../../include/hockey.h", "Makefile"]
 
 

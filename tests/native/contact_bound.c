@@ -1,6 +1,6 @@
 /* Test harness (tests/test_broadphase_bound.py): hill-climbs the ratio of the radius-free (core) distance to the
    total radius over player-vs-polygon configurations where the oracle's b2CollidePolygons restatement emits
-   contact points.  The kernel's collide broad phase (hk_arena.h pair_far_collide) rejects polygon pairs beyond
+   contact points.  The kernel's collide broad phase (hk_collide.h pair_far_collide) rejects polygon pairs beyond
    2 x total radius + kFarMargin; this measures how much of that bound contacts actually use. */
 #ifndef RESTARTS
 #define RESTARTS 300

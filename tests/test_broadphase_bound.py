@@ -1,4 +1,4 @@
-"""The collide broad phase (hk_arena.h pair_far_collide) rejects a polygon pair once a lower bound on the core
+"""The collide broad phase (hk_collide.h pair_far_collide) rejects a polygon pair once a lower bound on the core
 distance exceeds 2 x total radius + kFarMargin.  Box2D's b2CollidePolygons emits contact points only within
 about sqrt(2) x total radius of the cores for these shapes; this test hill-climbs the worst touching
 configuration with the oracle's restatement (tests/native/contact_bound.c) and requires it to stay well
