@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/hockey.h"
+#include "hk_arena_copy.h"
 #include "hk_host_step.h"
 #include "hk_kernels.h"
 
@@ -297,6 +298,65 @@ int hk_opponent_phase(void *ctx, double *phase_out, const double *phase_in, void
 
 int hk_opponent_phase3(void *ctx, double *phase_out, const double *phase_in, void *stream) {
   return phase_rows("hk_opponent_phase3", ctx, 3, phase_out, phase_in, stream);
+}
+
+// ---- exact arena snapshots, restore and fork (hk_arena_copy.h) ----
+static_assert(HK_CNT_BAD_INDEX < HK_NUM_COUNTERS, "the bad-index word is one of the context's counters");
+
+int64_t hk_snapshot_bytes(int64_t m) { return m < 0 ? 0 : hk::blob_layout(m).bytes; }
+
+int hk_snapshot_layout(int32_t *out5) {
+  if (!out5) return fail(HK_E_INVALID, "hk_snapshot_layout: NULL argument%s");
+  out5[0] = hk::NFF;
+  out5[1] = hk::NPW;
+  out5[2] = hk::kPhaseRows;
+  out5[3] = hk::NSOLID;
+  out5[4] = hk::NMF;
+  return HK_OK;
+}
+
+static int check_blob(const char *who, const void *blob, int64_t m) {
+  if (m < 0) return fail(HK_E_INVALID, "%s: negative count %lld", who, m);
+  if (m > 0 && !blob) return fail(HK_E_INVALID, "%s: blob is NULL", who);
+  if ((uintptr_t)blob & 15) return fail(HK_E_INVALID, "%s: blob is not 16-byte aligned", who);
+  return HK_OK;
+}
+
+int hk_snapshot(void *ctx, const int64_t *idx, int64_t m, void *blob, void *stream) {
+  HK_CTX(ctx, "hk_snapshot");
+  if (const int rc = check_blob("hk_snapshot", blob, m)) return rc;
+  HK_QUIESCED(c, "hk_snapshot");
+  return launched(hk::launch_copy_arenas(hk::blob_view(blob, m), nullptr, hk::view_of(c->s), idx, m,
+                                         c->s.counters + HK_CNT_BAD_INDEX, (hipStream_t)stream),
+                  "hk_snapshot");
+}
+
+int hk_restore(void *ctx, const int64_t *idx, int64_t m, const void *blob, int64_t blob_m, const int64_t *rows,
+               void *stream) {
+  HK_CTX(ctx, "hk_restore");
+  if (const int rc = check_blob("hk_restore", blob, m)) return rc;
+  if (blob_m < 0 || (m > 0 && blob_m == 0)) return fail(HK_E_INVALID, "hk_restore: bad blob_m %s%lld", "", blob_m);
+  HK_QUIESCED(c, "hk_restore");
+  return launched(hk::launch_copy_arenas(hk::view_of(c->s), idx, hk::blob_view(const_cast<void *>(blob), blob_m), rows,
+                                         m, c->s.counters + HK_CNT_BAD_INDEX, (hipStream_t)stream),
+                  "hk_restore");
+}
+
+int hk_copy_arenas(void *dst_ctx, const int64_t *dst_idx, void *src_ctx, const int64_t *src_idx, int64_t m,
+                   void *stream) {
+  if (!dst_ctx || !src_ctx) return fail(HK_E_INVALID, "hk_copy_arenas: ctx is NULL%s");
+  Ctx *d = (Ctx *)dst_ctx, *s = (Ctx *)src_ctx;
+  if (m < 0) return fail(HK_E_INVALID, "hk_copy_arenas: negative count %s%lld", "", m);
+  if (d->device != s->device) return fail(HK_E_INVALID, "hk_copy_arenas: the contexts are on different devices%s");
+  if (d->cfg.keep_mode != s->cfg.keep_mode || d->cfg.vel_ref != s->cfg.vel_ref)
+    return fail(HK_E_INVALID, "hk_copy_arenas: the contexts differ in keep_mode or vel_ref_semantics%s");
+  DeviceGuard g(d->device);
+  if (const int q = d->hs.quiesce("hk_copy_arenas")) return q;
+  if (s != d)
+    if (const int q = s->hs.quiesce("hk_copy_arenas")) return q;
+  return launched(hk::launch_copy_arenas(hk::view_of(d->s), dst_idx, hk::view_of(s->s), src_idx, m,
+                                         d->s.counters + HK_CNT_BAD_INDEX, (hipStream_t)stream),
+                  "hk_copy_arenas");
 }
 
 int hk_counters(void *ctx, int64_t *out, void *stream) {

@@ -39,6 +39,7 @@ constexpr hk::Scene g_scene =  // the kernels' compile-time scene (hk_scene_gen.
 
 #define SLDS g_scene  // the host build reads the one scene copy
 #include "../hk_step.h"
+#include "../hk_arena_copy.h"
 
 unsigned long long hk::g_hk_host_diag[4];
 unsigned long long hk::g_hk_flop_ev[hk::EV_N];
@@ -159,6 +160,52 @@ int hkh_flop_event_count(void) { return hk::EV_N; }
 void hkh_diag(unsigned long long *out4) {
   std::memcpy(out4, hk::g_hk_host_diag, sizeof(hk::g_hk_host_diag));
   std::memset(hk::g_hk_host_diag, 0, sizeof(hk::g_hk_host_diag));
+}
+
+// ---- exact arena copies (hk_arena_copy.h): the kernel's copy_entry / copy_arena, one list entry after the other ----
+constexpr int kCntBadIndex = 8;  // HK_CNT_BAD_INDEX (include/hockey.h)
+static void copy_list(const ArenaView &dst, const int64_t *dst_idx, const ArenaView &src, const int64_t *src_idx,
+                      int64_t m, unsigned long long *bad) {
+  for (int64_t e = 0; e < m; ++e) {
+    int64_t di, si;
+    if (copy_entry(dst, dst_idx, src, src_idx, e, di, si))
+      copy_arena(dst, di, src, si);
+    else
+      *bad += 1;
+  }
+}
+
+int64_t hkh_snapshot_bytes(int64_t m) { return m < 0 ? 0 : blob_layout(m).bytes; }
+
+void hkh_snapshot_layout(int32_t *out5) {
+  out5[0] = NFF;
+  out5[1] = NPW;
+  out5[2] = kPhaseRows;
+  out5[3] = NSOLID;
+  out5[4] = NMF;
+}
+
+// 0, or -1 for a blob that is not 16-byte aligned (as hk_snapshot / hk_restore: HK_E_INVALID)
+int hkh_snapshot(void *h, const int64_t *idx, int64_t m, void *blob) {
+  HostCtx *c = (HostCtx *)h;
+  if (m < 0 || ((uintptr_t)blob & 15)) return -1;
+  copy_list(blob_view(blob, m), nullptr, view_of(c->s), idx, m, &c->counters[kCntBadIndex]);
+  return 0;
+}
+
+int hkh_restore(void *h, const int64_t *idx, int64_t m, const void *blob, int64_t blob_m, const int64_t *rows) {
+  HostCtx *c = (HostCtx *)h;
+  if (m < 0 || blob_m < 0 || ((uintptr_t)blob & 15)) return -1;
+  copy_list(view_of(c->s), idx, blob_view(const_cast<void *>(blob), blob_m), rows, m, &c->counters[kCntBadIndex]);
+  return 0;
+}
+
+// -1 for contexts that differ in keep_mode or vel_ref (as hk_copy_arenas)
+int hkh_copy_arenas(void *dh, const int64_t *dst_idx, void *sh, const int64_t *src_idx, int64_t m) {
+  HostCtx *d = (HostCtx *)dh, *s = (HostCtx *)sh;
+  if (m < 0 || d->cfg.keep_mode != s->cfg.keep_mode || d->cfg.vel_ref != s->cfg.vel_ref) return -1;
+  copy_list(view_of(d->s), dst_idx, view_of(s->s), src_idx, m, &d->counters[kCntBadIndex]);
+  return 0;
 }
 
 void hkh_counters(void *h, unsigned long long *out16) {

@@ -4,6 +4,8 @@ Public surface:
   VecHockeyEnv                      N arenas on one GPU, torch tensors in/out (hockey_amd.vec_env)
   HockeyEnv, HockeyEnv_BasicOpponent, BasicOpponent, Mode, make
                                     the reference's single-env API (hockey_amd.hockey_env)
+  ArenaSnapshot, Lookahead          exact arena snapshots (VecHockeyEnv.snapshot / restore / fork) and K-way
+                                    lookahead over forked arenas (hockey_amd.snapshot, hockey_amd.lookahead)
 The compute path is libhockey_hip.so (csrc/, C ABI in include/hockey.h); torch only provides device
 memory and streams.
 """
@@ -17,4 +19,10 @@ def __getattr__(name):
     if name in ("HockeyEnv", "HockeyEnv_BasicOpponent", "BasicOpponent", "make", "register_envs"):
         from . import hockey_env
         return getattr(hockey_env, name)
+    if name == "ArenaSnapshot":
+        from .snapshot import ArenaSnapshot
+        return ArenaSnapshot
+    if name == "Lookahead":
+        from .lookahead import Lookahead
+        return Lookahead
     raise AttributeError(name)

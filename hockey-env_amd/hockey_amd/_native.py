@@ -20,6 +20,7 @@ POLICY_EXTERNAL, POLICY_RANDOM, POLICY_BASIC_WEAK, POLICY_BASIC_STRONG = 0, 1, 2
 STEP_SKIP_PHYSICS = 1
 DIAG_LARGE_ISLANDS = 1
 CNT_STEPS, CNT_EPISODES, CNT_GOALS_P1, CNT_GOALS_P2, CNT_TOI, CNT_OVERFLOW, CNT_LARGE_ISLANDS, CNT_BAD_POLICY = range(8)
+CNT_BAD_INDEX = 8  # snapshot / restore / copy entries with an index out of range (nothing copied); must stay 0
 
 
 class HockeyNativeError(RuntimeError):
@@ -44,14 +45,15 @@ EXPORTS = ["hk_last_error", "hk_version", "hk_create", "hk_destroy", "hk_num_are
            "hk_step", "hk_step_host", "hk_rollout", "hk_get_state", "hk_set_state", "hk_opponent_phase", "hk_opponent_phase3",
            "hk_observe", "hk_counters",
            "hk_reset_counters",
-           "hk_bytes_per_step", "hk_info"]
+           "hk_bytes_per_step", "hk_info",
+           "hk_snapshot_bytes", "hk_snapshot_layout", "hk_snapshot", "hk_restore", "hk_copy_arenas"]
 
 _lib = None
 
 # the files csrc/Makefile hashes into <lib>.srchash (HASHSRC = $(SRC) $(HDR) Makefile), in its order
-HASH_SOURCES = ["hk_kernels.hip", "hk_capi.cpp", "hk_host_step.cpp", "hk_core.h", "hk_geom.h", "hk_arena.h",
+HASH_SOURCES = ["hk_kernels.hip", "hk_arena_copy.hip", "hk_capi.cpp", "hk_host_step.cpp", "hk_core.h", "hk_geom.h", "hk_arena.h",
                 "hk_body.h", "hk_collide.h", "hk_world.h", "hk_game.h", "hk_solver.h", "hk_velocity.h", "hk_step.h",
-                "hk_kernels.h", "hk_host_step.h",
+                "hk_kernels.h", "hk_arena_copy.h", "hk_host_step.h",
                 "hk_scene_data.inc", "../../include/hockey.h", "Makefile"]
 
 
@@ -114,6 +116,14 @@ def lib():
     L.hk_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), vp]
     L.hk_reset_counters.argtypes = [vp, vp]
     L.hk_bytes_per_step.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    L.hk_snapshot_bytes.argtypes = [i64]
+    L.hk_snapshot_bytes.restype = i64
+    L.hk_snapshot_layout.argtypes = [ctypes.POINTER(ctypes.c_int32)]
+    L.hk_snapshot.argtypes = [vp, vp, i64, vp, vp]
+    L.hk_restore.argtypes = [vp, vp, i64, vp, i64, vp, vp]
+    L.hk_copy_arenas.argtypes = [vp, vp, vp, vp, i64, vp]
+    for name in ["hk_snapshot_layout", "hk_snapshot", "hk_restore", "hk_copy_arenas"]:
+        getattr(L, name).restype = i32
     for name in ["hk_create", "hk_destroy", "hk_set_policy", "hk_reset", "hk_step", "hk_step_host", "hk_rollout", "hk_get_state",
                  "hk_set_state",
                  "hk_observe", "hk_info", "hk_opponent_phase", "hk_opponent_phase3", "hk_counters", "hk_reset_counters", "hk_bytes_per_step"]:

@@ -261,6 +261,19 @@ class HockeyEnv:
         self._vec.set_state(raw[None, :], aux[None, :])
         self._refresh()
 
+    def snapshot(self):
+        """The arena's exact state (hockey_amd.snapshot.ArenaSnapshot): contacts, sleep times, pending force and
+        opponent phases included, which set_state -- like the reference's -- leaves alone."""
+        return self._vec.snapshot()
+
+    def restore(self, snap):
+        """Continue from ``snap`` bit for bit (a one-arena snapshot, e.g. arena k of a batch:
+        ``vec.snapshot([k])``).  The step server is stopped by the library and restarts with the next step."""
+        if snap.count != 1:
+            raise ValueError(f"HockeyEnv.restore needs a one-arena snapshot, got {snap.count} arenas")
+        self._vec.restore(snap)
+        self._refresh()
+
     @property
     def time(self):
         return int(self._snap.aux[2])
@@ -373,6 +386,10 @@ class HockeyEnv_BasicOpponent(HockeyEnv):
         _stage_actions(self._act_np, action)
         _PACK_INC(self._inc_np, 8, inc)
         return self._launch_step(None, opp_inc=True)
+
+    def restore(self, snap):
+        super().restore(snap)
+        self.opponent.phase = float(self._vec.opponent_phase()[0, 1])  # the host mirror follows the restored phase
 
 
 class PolicyOpponent:

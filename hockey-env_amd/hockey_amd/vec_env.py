@@ -11,6 +11,7 @@ onto the reference's per-env call, vectorised over a leading arena axis and kept
   obs_agent_two()          :500              obs_agent_two()  (or step(..., with_agent_two=True))
   get_info_agent_two()/get_reward_agent_two  returned by step(..., with_agent_two=True)
   set_state(s[18])         :594              set_state(state[N,18] raw, aux[N,5])
+  (none: set_state leaves contacts alone)    snapshot(indices) / restore(snap) / fork(src, dst, source): exact
   render("rgb_array")      :697              render(indices) -> uint8 [m,480,600,3] (any size, or palette indices)
   BasicOpponent.act        :787              policy=('external'|'random'|'weak'|'strong') per player
   ========================================  ================================================
@@ -71,6 +72,7 @@ class VecHockeyEnv:
         self.keep_mode = bool(keep_mode)
         self.mode = parse_mode(mode)
         self.auto_reset = bool(auto_reset)
+        self.vel_ref_semantics = bool(vel_ref_semantics)
         cfg = N.Config()
         cfg.keep_mode = int(self.keep_mode)
         cfg.mode = self.mode.value
@@ -304,6 +306,62 @@ class VecHockeyEnv:
         ax = None if aux is None else torch.as_tensor(aux, dtype=torch.int32, device=self.device).contiguous()
         mk = None if mask is None else torch.as_tensor(mask, dtype=torch.uint8, device=self.device).contiguous()
         N.check(self.L.hk_set_state(self._ctx, N.ptr(mk), N.ptr(st), N.ptr(ax), self._stream()), "hk_set_state")
+
+    # ------------------------------------------------------------------ exact snapshots / restore / fork
+    def snapshot(self, indices=None, assume_valid=False):
+        """The exact state of arenas ``indices`` (all when None) as an ArenaSnapshot on this device (hk_snapshot):
+        unlike get_state it carries contacts with their warm-start impulses, sleep times, the puck's pending force,
+        the BasicOpponent phases and the episode / step words that key the device draws, so a restore continues bit
+        for bit.  Counters and the host-side ``one_starts`` mirror that reset() toggles are not part of it.
+        Index checks run in torch (a host synchronisation) unless ``assume_valid``."""
+        from . import snapshot as S
+
+        idx = S.index_tensor(indices, self.device)
+        m = self.n if idx is None else idx.numel()
+        if not assume_valid:
+            S.check_indices(None, m, idx, self.n, m, what="snapshot")
+        # zeros: the sections' padding bytes are then defined, and equal arenas give equal blobs
+        blob = torch.zeros(S.snapshot_bytes(m), dtype=torch.uint8, device=self.device)
+        N.check(self.L.hk_snapshot(self._ctx, N.ptr(idx), m, N.ptr(blob), self._stream()), "hk_snapshot")
+        return S.ArenaSnapshot(blob, m, S.library_version(), S.library_layout(), self.keep_mode,
+                               self.vel_ref_semantics)
+
+    def restore(self, snap, indices=None, rows=None, assume_valid=False):
+        """Arena ``indices[e]`` (e when None) = row ``rows[e]`` (e when None) of ``snap`` (hk_restore).  A restore to
+        the index the row was taken from continues the identical device random stream; at another index the arena
+        continues with that index's stream (include/hockey.h).  A snapshot on another device is moved here first."""
+        from . import snapshot as S
+
+        snap.check(what="restore")
+        if snap.keep_mode != self.keep_mode or snap.vel_ref != self.vel_ref_semantics:
+            raise N.HockeyNativeError(
+                f"restore: snapshot written with keep_mode={snap.keep_mode}, vel_ref={snap.vel_ref}; this env has "
+                f"keep_mode={self.keep_mode}, vel_ref={self.vel_ref_semantics}")
+        if snap.device != self.device:
+            snap = snap.to(self.device)
+        idx, row = S.index_tensor(indices, self.device), S.index_tensor(rows, self.device)
+        m = idx.numel() if idx is not None else (row.numel() if row is not None else snap.count)
+        if not assume_valid:
+            S.check_indices(idx, self.n, row, snap.count, m, what="restore")
+        blob = snap.blob.contiguous()
+        N.check(self.L.hk_restore(self._ctx, N.ptr(idx), m, N.ptr(blob), snap.count, N.ptr(row), self._stream()),
+                "hk_restore")
+
+    def fork(self, src, dst=None, source=None, assume_valid=False):
+        """Copy arenas ``src`` of env ``source`` (default: this env) into arenas ``dst`` of this env (0..m-1 when
+        None), exactly (hk_copy_arenas).  A source index may repeat (one arena into K destinations); destinations
+        must be distinct and, within one env, disjoint from the sources.  Both envs share device, keep_mode and
+        vel_ref_semantics; mode and auto_reset may differ.  With ``assume_valid`` no check runs and the call is
+        fire-and-forget (legal inside a torch.cuda.graph capture when the index lists are device int64 tensors)."""
+        from . import snapshot as S
+
+        source = self if source is None else source
+        s, d = S.index_tensor(src, self.device), S.index_tensor(dst, self.device)
+        m = s.numel() if s is not None else (d.numel() if d is not None else min(self.n, source.n))
+        if not assume_valid:
+            S.check_indices(d, self.n, s, source.n, m, same_env=source is self, what="fork")
+        N.check(self.L.hk_copy_arenas(self._ctx, N.ptr(d), source._ctx, N.ptr(s), m, self._stream()),
+                "hk_copy_arenas")
 
     def opponent_phase(self, new_phase=None, rows=2):
         """Return the BasicOpponent phases [N,rows] (float64, device); optionally overwrite them.  rows=2:

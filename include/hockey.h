@@ -66,8 +66,11 @@ enum {
   HK_CNT_TOI = 4,       /* solved time-of-impact events */
   HK_CNT_OVERFLOW = 5,  /* island / TOI capacity overflows (must stay 0) */
   HK_CNT_LARGE_ISLANDS = 6, /* solver calls with more contacts than the register fast path holds */
-  HK_CNT_BAD_POLICY = 7     /* arena-steps whose io.policy2 entry was not an HK_POLICY_* id (that player
+  HK_CNT_BAD_POLICY = 7,    /* arena-steps whose io.policy2 entry was not an HK_POLICY_* id (that player
                                acted with zeros); must stay 0 */
+  HK_CNT_BAD_INDEX = 8      /* snapshot / restore / copy entries whose source or destination index was out of
+                               range (nothing was copied for them); must stay 0.  The phase-timer diagnostics build
+                               keeps its cycle sums in words 8..15 and shares this one */
 };
 
 typedef struct hk_config {
@@ -209,6 +212,47 @@ int hk_observe(void *ctx, float *obs, float *obs2, void *stream);
  *   info / info2     replace _get_info / get_info_agent_two            hockey/hockey_env.py:542-591
  *   reward / reward2 replace get_reward(_get_info()) / get_reward_agent_two(get_info_agent_two())  :518-540 */
 int hk_info(void *ctx, double *info, double *info2, double *reward, double *reward2, void *stream);
+
+/* Exact arena snapshots, restore and fork.
+ *
+ * hk_get_state / hk_set_state move what the reference's set_state moves (18 floats, 5 ints) and, like it, leave
+ * contacts and forces alone, so a step after hk_set_state is not the step the original arena would have taken.
+ * These calls move EVERY word of an arena that outlives a step: the body rows with centres of mass and sleep
+ * times, the puck's pending force, the packed int words (touching / enabled / awake bits, done, winner,
+ * one_starts, has_puck, max_t, time, and the episode / step words that key the device draws), the three
+ * BasicOpponent phase rows and all manifold records with their warm-start impulses, touching or not.
+ * An arena restored or copied this way continues bit for bit as its source would have.
+ *
+ * hk_snapshot_bytes(m): size of a blob of m arenas.  A blob is DEVICE memory, 16-B aligned, and opaque: its layout
+ * follows the library's internal enums, so a blob is valid only for the hk_version() that wrote it.
+ * hk_snapshot_layout: out[5] (host) = float rows, packed int words, phase rows, manifold records per arena, words
+ * per record -- the numbers a wrapper stores beside a blob to refuse one written under another layout.
+ * hk_snapshot: blob row e = arena idx[e] of ctx, e < m (idx NULL: arena e).
+ * hk_restore:  arena idx[e] of ctx = blob row rows[e], e < m (idx NULL: arena e; rows NULL: row e); blob_m is the
+ *              row count the blob was written with.
+ * hk_copy_arenas: arena dst_idx[e] of dst_ctx = arena src_idx[e] of src_ctx, e < m (a NULL list: e).  dst_ctx may
+ *              be src_ctx (a fork inside one context).  Both contexts must be on the same device with equal
+ *              keep_mode and vel_ref_semantics (HK_E_INVALID otherwise); mode and auto_reset may differ: they
+ *              act at the next reset only, and max_t travels with the arena.
+ * Index lists are int64 DEVICE arrays.  An entry whose source or destination index is out of range copies nothing
+ * and adds one to HK_CNT_BAD_INDEX of the destination context (of ctx for hk_snapshot); that counter must stay 0.
+ * CALLER'S CONTRACT, not checked here: destination indices are distinct, and within one context no destination
+ * is also a source (the entries are copied concurrently).  The Python layer checks both.
+ * All four are fire-and-forget on `stream` and legal under stream capture; every context involved is quiesced
+ * first, so its hk_step_host server never runs beside a copy.
+ * Counters are per context and are not part of a snapshot.
+ * Device draws (fused HK_POLICY_RANDOM actions, BasicOpponent phase increments with io.opp_inc == NULL, auto-reset
+ * placement) are keyed by the GLOBAL id of the arena that is stepping (arena_offset + index) and the arena's own
+ * episode / step words.  A restore to the same index therefore continues the identical random stream; a copy to
+ * another index continues with that index's stream.  With external actions or given opp_inc, and no auto-reset,
+ * the continuation is identical at any index. */
+int64_t hk_snapshot_bytes(int64_t m);
+int hk_snapshot_layout(int32_t *out5);
+int hk_snapshot(void *ctx, const int64_t *idx, int64_t m, void *blob, void *stream);
+int hk_restore(void *ctx, const int64_t *idx, int64_t m, const void *blob, int64_t blob_m, const int64_t *rows,
+               void *stream);
+int hk_copy_arenas(void *dst_ctx, const int64_t *dst_idx, void *src_ctx, const int64_t *src_idx, int64_t m,
+                   void *stream);
 
 /* counters: out[HK_NUM_COUNTERS] int64 on the HOST (synchronises the stream). */
 int hk_counters(void *ctx, int64_t *out, void *stream);
