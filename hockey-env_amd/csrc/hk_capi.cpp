@@ -44,6 +44,10 @@ struct Ctx {
   hk::DevState s{};
   hk::KCfg cfg{};
   hk::HostStep hs;  // hk_step_host's buffer and resident step server (hk_host_step.h)
+  // hk_reset_seeded's scratch: the placement kernel's params [N,6] and puck sides [N], read by the reset launch
+  // that follows it on the same stream (allocated at hk_create: no allocation on the call path)
+  float *seed_params = nullptr;
+  uint8_t *seed_one = nullptr;
 };
 
 int check_policy(int p) { return p >= HK_POLICY_EXTERNAL && p <= HK_POLICY_BASIC_STRONG; }
@@ -131,7 +135,9 @@ int hk_create(int device, int64_t n, const hk_config *cfg, void **out) {
   const size_t nw = (size_t)hk::workspace_words_per_arena() * n;
   if ((e = hipMalloc(&c->s.f, nf * 4)) != hipSuccess || (e = hipMalloc(&c->s.i, ni * 4)) != hipSuccess ||
       (e = hipMalloc(&c->s.man, nm * 4)) != hipSuccess || (e = hipMalloc(&c->s.phase, 3 * n * 8)) != hipSuccess ||
-      (e = hipMalloc(&c->s.ws, nw * 4)) != hipSuccess || (e = hipMalloc(&c->s.counters, HK_NUM_COUNTERS * 8)) != hipSuccess) {
+      (e = hipMalloc(&c->s.ws, nw * 4)) != hipSuccess || (e = hipMalloc(&c->s.counters, HK_NUM_COUNTERS * 8)) != hipSuccess ||
+      (e = hipMalloc(&c->seed_params, (size_t)HK_PARAM_DIM * n * 4)) != hipSuccess ||
+      (e = hipMalloc(&c->seed_one, (size_t)n)) != hipSuccess) {
     hk_destroy(c);
     return hipfail(e, "hk_create: hipMalloc");
   }
@@ -172,6 +178,8 @@ int hk_destroy(void *ctx) {
   if (c->s.ws) (void)hipFree(c->s.ws);
   if (c->s.phase) (void)hipFree(c->s.phase);
   if (c->s.counters) (void)hipFree(c->s.counters);
+  if (c->seed_params) (void)hipFree(c->seed_params);
+  if (c->seed_one) (void)hipFree(c->seed_one);
   delete c;
   return HK_OK;
 }
@@ -222,6 +230,34 @@ int hk_reset(void *ctx, const uint8_t *mask, const float *params, const int32_t 
     if (rc != HK_OK) return rc;
   }
   return launched(hk::launch_reset(c->s, c->cfg, mask, params, max_t, one_starts, (hipStream_t)stream), "hk_reset");
+}
+
+int hk_seeded_params(void *ctx, const uint64_t *seeds, const uint8_t *one_starts, float *params, int32_t *max_t,
+                     void *stream) {
+  HK_CTX(ctx, "hk_seeded_params");
+  if (!seeds || !params) return fail(HK_E_INVALID, "hk_seeded_params: NULL argument%s");
+  HK_QUIESCED(c, "hk_seeded_params");
+  return launched(hk::launch_seeded_params(c->s, c->cfg, nullptr, seeds, one_starts, 0, params, max_t, nullptr,
+                                           (hipStream_t)stream),
+                  "hk_seeded_params");
+}
+
+// Two launches on `stream`: the placement kernel (hk_seeded_reset.hip) into the context's scratch, then hk_reset's
+// own kernel with that scratch as its explicit params and puck sides -- the reset itself stays single source.
+int hk_reset_seeded(void *ctx, const uint8_t *mask, const uint64_t *seeds, const int32_t *max_t,
+                    const uint8_t *one_starts, void *stream) {
+  HK_CTX(ctx, "hk_reset_seeded");
+  if (!seeds) return fail(HK_E_INVALID, "hk_reset_seeded: seeds is NULL%s");
+  HK_QUIESCED(c, "hk_reset_seeded");
+  if (max_t) {
+    const int rc = check_ints("hk_reset_seeded", c->s.n, 1, max_t, mask, (hipStream_t)stream);
+    if (rc != HK_OK) return rc;
+  }
+  const hipError_t e = hk::launch_seeded_params(c->s, c->cfg, mask, seeds, one_starts, 1, c->seed_params, nullptr,
+                                                c->seed_one, (hipStream_t)stream);
+  if (e != hipSuccess) return hipfail(e, "hk_reset_seeded");
+  return launched(hk::launch_reset(c->s, c->cfg, mask, c->seed_params, max_t, c->seed_one, (hipStream_t)stream),
+                  "hk_reset_seeded");
 }
 
 static int launch_steps(const char *who, void *ctx, const hk_step_io *io, int nsteps, void *stream) {

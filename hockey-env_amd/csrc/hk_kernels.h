@@ -115,6 +115,12 @@ hipError_t launch_get_state(const DevState &s, const KCfg &cfg, float *state, in
 hipError_t launch_set_state(const DevState &s, const KCfg &cfg, const uint8_t *mask, const float *state,
                             const int32_t *aux, hipStream_t st);
 int64_t workspace_words_per_arena();
+// hk_seeded_reset.hip: the reference's PCG64 placement of seeds[a] for the arenas the mask selects, for the puck
+// side one_in[a], or (one_in NULL) the arena's stored flag, toggled first in NORMAL mode when `toggle`.  Writes
+// params [N,6], max_t [N] (or NULL) and the side drawn for into one_out [N] (or NULL); no arena word.
+hipError_t launch_seeded_params(const DevState &s, const KCfg &cfg, const uint8_t *mask, const uint64_t *seeds,
+                                const uint8_t *one_in, int toggle, float *params, int32_t *max_t, uint8_t *one_out,
+                                hipStream_t st);
 
 // host-side scene construction (hk_scene.cpp): Box2D 2.3 hull / normals / mass data of hockey_env.py's
 // fixtures, and the canonical contact pair table.  Run at build time by hk_scene_gen.cpp, whose output

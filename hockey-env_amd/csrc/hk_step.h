@@ -14,6 +14,7 @@
 //                               override (global np.random stream -> per-arena Philox)
 #pragma once
 #include "hk_arena.h"
+#include "hk_seed.h"
 
 namespace hk {
 
@@ -269,10 +270,9 @@ HK_DEV void reset_arena(Arena &w, const float *p6, int max_t) {
   w.winner = 0;
 }
 
-// device placement (same formulas as hockey_amd/placement.py with Philox uniforms instead of PCG64)
+// device placement: hk_seed.h's placement_law (hockey_amd/placement.py's formulas) on Philox uniforms instead of PCG64
 HK_DEV void device_placement(uint64_t seed, int64_t a, uint32_t episode, int mode, int one_starts, float *p6,
                              int &max_t) {
-  const double W = 10.0, H = 8.0;
   U4 r0 = philox(seed, (uint32_t)a, (uint32_t)(a >> 32), episode, RNG_RESET);
   U4 r1 = philox(seed, (uint32_t)a, (uint32_t)(a >> 32), episode, RNG_RESET + 0x100);
   const double u0 = u01d(r0.x, r0.y), u1 = u01d(r0.z, r0.w), u2 = u01d(r1.x, r1.y), u3 = u01d(r1.z, r1.w);
@@ -284,35 +284,7 @@ HK_DEV void device_placement(uint64_t seed, int64_t a, uint32_t episode, int mod
     ++k;
     return lo + (hi - lo) * x;
   };
-  max_t = mode == 0 ? 250 : 80;
-  double p2x = 4 * W / 5, p2y = H / 2;
-  if (mode != 0) {
-    p2x = 4 * W / 5 + unif(-W / 3, W / 6);
-    p2y = H / 2 + unif(-H / 4, H / 4);
-  }
-  double px, py;
-  float fx = 0.0f, fy = 0.0f;
-  if (mode == 0 || mode == 1) {
-    if (one_starts || mode == 1) {
-      px = W / 2 - unif(H / 8, H / 4);
-      py = H / 2 + unif(-H / 8, H / 8);
-    } else {
-      px = W / 2 + unif(H / 8, H / 4);
-      py = H / 2 + unif(-H / 8, H / 8);
-    }
-  } else {
-    px = W / 2 + unif(0, W / 3);
-    py = H / 2 + 0.8 * unif(-H / 2, H / 2);
-    float aim = (float)(H / 2 + .6 * unif(-75.0 / 60.0, 75.0 / 60.0));
-    float dx = (float)px - 0.0f, dy = (float)py - aim;
-    float ln = sqrtf(dx * dx + dy * dy);
-    dx = dx / ln;
-    dy = dy / ln;
-    const float m = g_scene.mass[B_PK];
-    fx = ((-dx * 60.0f) * m) / 0.02f;
-    fy = ((-dy * 60.0f) * m) / 0.02f;
-  }
-  p6[0] = (float)p2x; p6[1] = (float)p2y; p6[2] = (float)px; p6[3] = (float)py; p6[4] = fx; p6[5] = fy;
+  placement_law(unif, mode, one_starts, p6, max_t);
 }
 
 HK_DEV void write_info(float *dst, int64_t a, const double *info) {

@@ -46,13 +46,14 @@ EXPORTS = ["hk_last_error", "hk_version", "hk_create", "hk_destroy", "hk_num_are
            "hk_observe", "hk_counters",
            "hk_reset_counters",
            "hk_bytes_per_step", "hk_info",
-           "hk_snapshot_bytes", "hk_snapshot_layout", "hk_snapshot", "hk_restore", "hk_copy_arenas"]
+           "hk_snapshot_bytes", "hk_snapshot_layout", "hk_snapshot", "hk_restore", "hk_copy_arenas",
+           "hk_seeded_params", "hk_reset_seeded"]
 
 _lib = None
 
 # the files csrc/Makefile hashes into <lib>.srchash (HASHSRC = $(SRC) $(HDR) Makefile), in its order
-HASH_SOURCES = ["hk_kernels.hip", "hk_arena_copy.hip", "hk_capi.cpp", "hk_host_step.cpp", "hk_core.h", "hk_geom.h", "hk_arena.h",
-                "hk_body.h", "hk_collide.h", "hk_world.h", "hk_game.h", "hk_solver.h", "hk_velocity.h", "hk_step.h",
+HASH_SOURCES = ["hk_kernels.hip", "hk_arena_copy.hip", "hk_seeded_reset.hip", "hk_capi.cpp", "hk_host_step.cpp", "hk_core.h", "hk_geom.h", "hk_arena.h",
+                "hk_body.h", "hk_collide.h", "hk_world.h", "hk_game.h", "hk_solver.h", "hk_velocity.h", "hk_seed.h", "hk_step.h",
                 "hk_kernels.h", "hk_arena_copy.h", "hk_host_step.h",
                 "hk_scene_data.inc", "../../include/hockey.h", "Makefile"]
 
@@ -104,6 +105,8 @@ def lib():
     L.hk_num_arenas.restype = i64
     L.hk_set_policy.argtypes = [vp, i32, i32]
     L.hk_reset.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.hk_seeded_params.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.hk_reset_seeded.argtypes = [vp, vp, vp, vp, vp, vp]
     L.hk_step.argtypes = [vp, ctypes.POINTER(StepIO), vp]
     L.hk_rollout.argtypes = [vp, i32, ctypes.POINTER(StepIO), vp]
     L.hk_step_host.argtypes = [vp, vp, vp, i32, vp, vp]
@@ -122,7 +125,8 @@ def lib():
     L.hk_snapshot.argtypes = [vp, vp, i64, vp, vp]
     L.hk_restore.argtypes = [vp, vp, i64, vp, i64, vp, vp]
     L.hk_copy_arenas.argtypes = [vp, vp, vp, vp, i64, vp]
-    for name in ["hk_snapshot_layout", "hk_snapshot", "hk_restore", "hk_copy_arenas"]:
+    for name in ["hk_snapshot_layout", "hk_snapshot", "hk_restore", "hk_copy_arenas", "hk_seeded_params",
+                 "hk_reset_seeded"]:
         getattr(L, name).restype = i32
     for name in ["hk_create", "hk_destroy", "hk_set_policy", "hk_reset", "hk_step", "hk_step_host", "hk_rollout", "hk_get_state",
                  "hk_set_state",

@@ -77,16 +77,35 @@ def reset_params(episodes, seed, mode=Mode.NORMAL, first_reset=0):
     return params, max_t, one
 
 
+def reset_episodes(env, episodes, seed, mode=Mode.NORMAL, first_reset=0, index=None, placement="device"):
+    """Reset ``env`` so that arena a starts episode ``index[a]`` (a when None) of ``reset_params(episodes, seed,
+    mode, first_reset)``; returns that mode's max_timesteps.  placement="device" draws on the GPU
+    (VecHockeyEnv.reset_seeded with seeds ``seed + i`` and reset_params' puck sides): no host draw, no upload of
+    params; "host" is reset_params and an upload.  Both leave the same bodies, hence the same episodes; reset_params
+    stays the host statement of the law the tests hold the kernel to."""
+    if placement not in ("device", "host"):
+        raise ValueError("placement must be 'device' or 'host'")
+    if placement == "host":
+        params, max_t, _ = reset_params(episodes, seed, mode, first_reset)
+        env.reset_params(params if index is None else params[index])
+        return max_t
+    i = np.arange(episodes, dtype=np.int64) if index is None else np.asarray(index, np.int64)
+    env.reset_seeded([int(seed) + int(k) for k in i], one_starting=((first_reset + i) % 2) == 1)
+    return 250 if env.mode == Mode.NORMAL else 80  # hockey_env.py:357 (placement()'s max_timesteps)
+
+
 @torch.no_grad()
 def evaluate(policy, episodes=100, seed=42, weak_opponent=False, mode=Mode.NORMAL, device="cuda:0",
-             player1=None, replicas=1, opponent_phase="walked", phase_seed=None, per_episode=False):
+             player1=None, replicas=1, opponent_phase="walked", phase_seed=None, per_episode=False,
+             placement="device"):
     """Win rate and mean return of ``policy`` (obs [N,18] tensor -> actions [N,4]) against BasicOpponent.
 
     ``player1`` = "strong" / "weak" evaluates the fused BasicOpponent as player 1 instead of ``policy``
     (the reference notebook's BasicOpponent-vs-BasicOpponent study).  ``replicas``, ``opponent_phase``: see the
     module docstring; ``phase_seed`` seeds the walked phases (default ``seed``).  Returns a dict with win / draw /
     loss rates, mean return and mean episode length over all replicas x episodes games; ``per_episode`` adds
-    ``winner`` [replicas, episodes] (+1 / 0 / -1)."""
+    ``winner`` [replicas, episodes] (+1 / 0 / -1).  placement: where the reset placements are drawn
+    (reset_episodes; the same episodes either way)."""
     from .vec_env import VecHockeyEnv
 
     if opponent_phase not in ("walked", "fresh"):
@@ -96,8 +115,7 @@ def evaluate(policy, episodes=100, seed=42, weak_opponent=False, mode=Mode.NORMA
     p1 = player1 if player1 is not None else "external"
     env = VecHockeyEnv(n, keep_mode=True, mode=mode, device=device,
                        policies=(p1, "weak" if weak_opponent else "strong"), auto_reset=False, seed=seed)
-    params, max_t, _ = reset_params(episodes, seed, mode)
-    env.reset_params(np.tile(params, (reps, 1)))
+    max_t = reset_episodes(env, episodes, seed, mode, index=np.tile(np.arange(episodes), reps), placement=placement)
     if opponent_phase == "walked":
         rng = np.random.default_rng(seed if phase_seed is None else phase_seed)
         env.opponent_phase(rng.uniform(0, 2 * np.pi, (n, 2)))
@@ -157,7 +175,7 @@ def tournament_fold(winner, length, n_actors, games, include_bots=True):
 
 @torch.no_grad()
 def tournament(actors, games=20, seed=42, include_bots=True, backend="auto", per_game=False, mode=Mode.NORMAL,
-               device="cuda:0", on_step=None):
+               device="cuda:0", on_step=None, placement="device"):
     """Cross-play: every ordered pair of ``actors`` (K Actor modules or state dicts; actor i as player 1 against
     actor j as player 2, i == j included) plays ``games`` games, all K * cols * games arenas stepping together in
     one VecHockeyEnv batch.  With ``include_bots`` two more opponent columns play the weak (column K) and the strong
@@ -170,7 +188,7 @@ def tournament(actors, games=20, seed=42, include_bots=True, backend="auto", per
 
     Returns a dict of [K][cols] float arrays ``win`` / ``draw`` / ``loss`` (of the row actor), ``mean_length`` and
     ``score`` = win + 0.5 draw; ``per_game`` adds ``winner`` [K][cols][games] int8.  on_step(obs, obs2, actions)
-    sees every step's inputs and the actions played (test hook)."""
+    sees every step's inputs and the actions played (test hook).  placement: as in ``evaluate``."""
     from .policy_bank import PolicyBank
     from .vec_env import VecHockeyEnv, _POLICIES
 
@@ -183,8 +201,7 @@ def tournament(actors, games=20, seed=42, include_bots=True, backend="auto", per
         bank.add(a)
     env = VecHockeyEnv(n, keep_mode=True, mode=mode, device=dev, policies=("external", "external"), auto_reset=False,
                        seed=seed)
-    params, max_t, _ = reset_params(games, seed, mode)
-    env.reset_params(params[g])
+    max_t = reset_episodes(env, games, seed, mode, index=g, placement=placement)
     env.opponent_phase(np.random.default_rng(seed).uniform(0, 2 * np.pi, (n, 3)), rows=3)
     ids = np.where(p2 >= 0, _POLICIES["external"], np.where(p2 == -1, _POLICIES["weak"], _POLICIES["strong"]))
     policy2 = torch.as_tensor(ids.astype(np.uint8), device=dev)

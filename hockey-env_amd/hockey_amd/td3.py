@@ -36,6 +36,7 @@ import json
 import math
 from dataclasses import dataclass, fields
 
+import numpy as np
 import torch
 
 from .constants import Mode
@@ -612,8 +613,9 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
     Replay capacity: ``cfg.buffer_size``, raised to one full round of every arena (``n_arenas * max_steps``)
     when that is larger, so sampled data always spans whole episodes (65 536 arenas x 500 steps = 5.5 GB of
     HBM at C5).  reset: "seeded" places episode e (1-based, arena i of round k: e = k*N + i + 1) like
-    ``reset(seed=seed + e)`` (the reference's PCG64 stream, drawn on the host: ~0.5 s per round at 65 536
-    arenas); "device" uses the kernel's Philox placement (same distribution, no host work).
+    ``reset(seed=seed + e)``: the reference's PCG64 stream, drawn by the kernel (VecHockeyEnv.reset_seeded) when
+    the env has it, else on the host; "seeded_host" always draws on the host (~0.5 s per round at 65 536 arenas,
+    kept for A/B: the same episodes); "device" uses the kernel's Philox placement (same distribution).
     eval_fn(agent, episodes_done) is called every ``cfg.eval_interval`` episodes.  timing: synchronise around each
     round's collection and updates and record their wall seconds in ``stats["round_time"]``.  Returns
     (agent, stats).  fused: the learner path (Learner).  env: a VecHockeyEnv-shaped batch of n_arenas arenas to train on (default: a new
@@ -646,6 +648,8 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
     cfg = cfg or TD3Config()
     if per_sampler not in ("torch", "device"):
         raise ValueError("per_sampler must be 'torch' or 'device'")
+    if reset not in ("seeded", "seeded_host", "device"):
+        raise ValueError("reset must be 'seeded', 'seeded_host' or 'device'")
     curriculum = cfg.curriculum_name if curriculum is None else curriculum
     use_self_play = cfg.use_self_play if use_self_play is None else use_self_play
     self_play_interval = cfg.self_play_interval if self_play_interval is None else self_play_interval
@@ -689,6 +693,11 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
         mix.update_schedule((episodes + 1) / (rounds * n_arenas))  # update_schedule(ep, max_episodes)
         if reset == "device":
             obs, obs2 = (t.clone() for t in env.reset())
+        elif reset == "seeded" and hasattr(env, "reset_seeded"):
+            # the same episodes as below, drawn by the kernel: seeds and puck sides are reset_params' own
+            e = np.arange(rnd * n_arenas, (rnd + 1) * n_arenas, dtype=np.int64)
+            seeds = torch.arange(seed + 1 + rnd * n_arenas, seed + 1 + (rnd + 1) * n_arenas, device=env.device)
+            obs, obs2 = (t.clone() for t in env.reset_seeded(seeds, one_starting=(e % 2) == 1))
         else:
             # episode e = rnd * N + i + 1 is the train env's e-th reset: seed + e, puck side toggling per reset
             p, _, _ = reset_params(n_arenas, seed + rnd * n_arenas + 1, mode, first_reset=rnd * n_arenas)

@@ -6,7 +6,8 @@ onto the reference's per-env call, vectorised over a leading arena axis and kept
   ========================================  ================================================
   reference (one env, numpy, host)          VecHockeyEnv (N arenas, torch tensors on cuda)
   ========================================  ================================================
-  reset(seed=s)            :345              reset(seeds=[...]) / reset() (device placement)
+  reset(seed=s)            :345              reset_seeded(seeds) (PCG64 draws on the device) / reset(seeds=[...])
+                                             (the same on the host) / reset() (device Philox placement)
   step(a[8]) -> obs,r,d,_,info :658          step(actions[N,8]) -> obs[N,18], r[N], d[N], info
   obs_agent_two()          :500              obs_agent_two()  (or step(..., with_agent_two=True))
   get_info_agent_two()/get_reward_agent_two  returned by step(..., with_agent_two=True)
@@ -27,6 +28,8 @@ from . import _native as N
 
 from .constants import Mode, parse_mode
 from .placement import np_random, placement
+
+_host_placement = placement  # reset() has a keyword of the same name
 
 # torch's private accessor for the current raw stream (no Stream object per call); the public form is the fallback,
 # and tests/test_gpu_facade.py holds the two equal inside and outside a torch.cuda.stream context
@@ -128,14 +131,9 @@ class VecHockeyEnv:
         self.policies[player] = pid
 
     # ------------------------------------------------------------------ reset
-    def reset(self, seeds=None, mask=None, one_starting=None):
-        """HockeyEnv.reset for the selected arenas.
-
-        seeds: None -> device Philox placement; int / sequence -> the reference's PCG64 draws per arena
-        (bit-identical placement to ``HockeyEnv.reset(seed=s)``).  one_starting: None toggles like the
-        reference (NORMAL mode), a bool / bool array forces the puck side.
-        Returns (obs[N,18], info[N,4]) tensors (agent-1 frame) for all arenas.
-        """
+    def _mirror_one_starts(self, mask, one_starting):
+        """Advance the host mirror ``self.one_starts`` as a reset of the arenas ``mask`` selects does (NORMAL mode:
+        toggle, or take ``one_starting``); returns the selection as a bool array."""
         n = self.n
         sel = np.ones(n, bool) if mask is None else np.asarray(mask.cpu() if torch.is_tensor(mask) else mask, bool)
         if self.mode == Mode.NORMAL:
@@ -143,6 +141,93 @@ class VecHockeyEnv:
                 self.one_starts = np.where(sel, ~self.one_starts, self.one_starts)
             else:
                 self.one_starts = np.where(sel, np.broadcast_to(np.asarray(one_starting, bool), (n,)), self.one_starts)
+        return sel
+
+    def _seed_tensor(self, seeds):
+        """``seeds`` (int, sequence, numpy array or device int64 / uint64 tensor) as the [N] device words
+        hk_seeded_params / hk_reset_seeded read: uint64 seeds, which a non-negative int64 tensor already is byte for
+        byte.  Negative seeds raise ValueError, as gymnasium's np_random does (a device int64 tensor is checked with
+        one reduction, a host synchronisation, except under stream capture); None and seeds >= 2**64 have no device
+        form and raise too."""
+        n = self.n
+        if torch.is_tensor(seeds):
+            t = seeds.to(self.device)
+            if t.dtype not in (torch.int64, torch.uint64):
+                raise ValueError(f"seeds tensor must be int64 or uint64, got {t.dtype}")
+            t = t.expand(n) if t.dim() == 0 else t
+            if t.shape != (n,):
+                raise ValueError(f"seeds must have shape ({n},), got {tuple(t.shape)}")
+            if t.dtype == torch.int64 and not torch.cuda.is_current_stream_capturing() and bool((t < 0).any()):
+                raise ValueError("seeds must be non-negative")
+            return t.contiguous()
+        arr = np.asarray(seeds)
+        if arr.dtype.kind not in "iu":  # Python ints past int64 (object arrays), None, mixed input: one by one
+            vals = list(np.broadcast_to(np.asarray(seeds, dtype=object), (n,)))
+            if any(s is None for s in vals):
+                raise ValueError("device placement needs explicit seeds (seed=None draws OS entropy on the host)")
+            vals = [int(s) for s in vals]
+            if any(s >= 1 << 64 for s in vals):
+                raise ValueError("device placement takes seeds below 2**64")
+            arr = np.array(vals, dtype=object)
+        if (arr < 0).any():
+            raise ValueError("seeds must be non-negative")
+        arr = np.array(np.broadcast_to(arr, (n,)), dtype=np.uint64)  # a copy: contiguous and writable
+        # the uint64 bytes travel as an int64 tensor (torch's uint64 support is partial); the kernel reads uint64
+        return torch.as_tensor(arr.view(np.int64), device=self.device)
+
+    def seeded_params(self, seeds, one_starting=None):
+        """The placement ``HockeyEnv.reset(seed=seeds[a])`` draws for arena a in this env's mode, drawn on the
+        device (hk_seeded_params): (params [N,6] float32, max_t [N] int32), byte-equal to
+        ``hockey_amd.placement.placement``.  one_starting: the puck side per arena (bool / bool array); None = each
+        arena's stored flag as it stands.  Touches no arena and not the ``one_starts`` mirror."""
+        st = self._seed_tensor(seeds)
+        one_t = None
+        if one_starting is not None:
+            one = np.broadcast_to(np.asarray(one_starting.cpu() if torch.is_tensor(one_starting) else one_starting,
+                                             bool), (self.n,))
+            one_t = torch.as_tensor(one.astype(np.uint8), device=self.device)
+        params = torch.empty((self.n, N.PARAM_DIM), dtype=torch.float32, device=self.device)
+        max_t = torch.empty((self.n,), dtype=torch.int32, device=self.device)
+        N.check(self.L.hk_seeded_params(self._ctx, N.ptr(st), N.ptr(one_t), N.ptr(params), N.ptr(max_t),
+                                        self._stream()), "hk_seeded_params")
+        return params, max_t
+
+    def reset_seeded(self, seeds, mask=None, one_starting=None, max_t=None):
+        """``HockeyEnv.reset(seed=seeds[a])`` for the selected arenas with the reference's PCG64 placement drawn on
+        the device (hk_reset_seeded): the state ``reset(seeds=...)`` leaves, with no host draw and no upload.
+        seeds: see _seed_tensor.  one_starting: None toggles like the reference (NORMAL mode), a bool / bool array
+        forces the puck side; the ``one_starts`` mirror follows exactly as in reset().  max_t ([N] int32,
+        optional) overrides the mode's max_timesteps and makes the call synchronous (range check).  With a device
+        seeds tensor and no mask, one_starting or max_t, nothing is uploaded and the call is fire-and-forget: legal
+        inside a torch.cuda.graph capture (the mirror advances once, at capture, not per replay).
+        Returns observe()."""
+        st = self._seed_tensor(seeds)
+        sel = self._mirror_one_starts(mask, one_starting)
+        mask_t = None if mask is None else torch.as_tensor(sel.astype(np.uint8), device=self.device)
+        one_t = None
+        if one_starting is not None:
+            one_t = torch.as_tensor(self.one_starts.astype(np.uint8), device=self.device)
+        mt = None if max_t is None else torch.as_tensor(max_t, dtype=torch.int32, device=self.device).contiguous()
+        N.check(self.L.hk_reset_seeded(self._ctx, N.ptr(mask_t), N.ptr(st), N.ptr(mt), N.ptr(one_t), self._stream()),
+                "hk_reset_seeded")
+        return self.observe()
+
+    def reset(self, seeds=None, mask=None, one_starting=None, placement="host"):
+        """HockeyEnv.reset for the selected arenas.
+
+        seeds: None -> device Philox placement; int / sequence -> the reference's PCG64 draws per arena
+        (bit-identical placement to ``HockeyEnv.reset(seed=s)``).  one_starting: None toggles like the
+        reference (NORMAL mode), a bool / bool array forces the puck side.  placement: where explicit seeds are
+        drawn -- "host" (numpy, one Generator per arena, then uploaded) or "device" (reset_seeded: the same
+        placement from the kernel; every seed must be an int in [0, 2**64)).
+        Returns (obs[N,18], info[N,4]) tensors (agent-1 frame) for all arenas.
+        """
+        if placement not in ("host", "device"):
+            raise ValueError("placement must be 'host' or 'device'")
+        if placement == "device" and seeds is not None:
+            return self.reset_seeded(seeds, mask=mask, one_starting=one_starting)
+        n = self.n
+        sel = self._mirror_one_starts(mask, one_starting)
         one_t = torch.as_tensor(self.one_starts.astype(np.uint8), device=self.device)
         mask_t = None if mask is None else torch.as_tensor(sel.astype(np.uint8), device=self.device)
         params_t = None
@@ -151,7 +236,7 @@ class VecHockeyEnv:
             params = np.zeros((n, N.PARAM_DIM), np.float32)
             for i in np.nonzero(sel)[0]:
                 rng, _ = np_random(None if seeds[i] is None else int(seeds[i]))
-                params[i], _ = placement(self.mode, bool(self.one_starts[i]), rng)
+                params[i], _ = _host_placement(self.mode, bool(self.one_starts[i]), rng)
             params_t = torch.as_tensor(params, device=self.device)
         N.check(self.L.hk_reset(self._ctx, N.ptr(mask_t), N.ptr(params_t), None, N.ptr(one_t), self._stream()),
                 "hk_reset")

@@ -2,6 +2,7 @@
  *
  * Drop-in boundary for the reference's per-step hot path (julilili42/hockey-env):
  *   hk_reset           replaces HockeyEnv.reset            hockey/hockey_env.py:345-418
+ *   hk_reset_seeded    replaces HockeyEnv.reset(seed=s)    ... with np_random(seed) and r_uniform (:180-181) on the device
  *   hk_step            replaces HockeyEnv.step             hockey/hockey_env.py:658-695
  *                      (+ HockeyEnv_BasicOpponent.step     hockey/hockey_env.py:882-886 via policies)
  *     io.obs2/reward2  replace obs_agent_two / get_info_agent_two / get_reward_agent_two
@@ -147,6 +148,30 @@ int hk_set_policy(void *ctx, int player, int policy);
  * synchronised for the range check before the reset is launched, so such a call is illegal under stream capture. */
 int hk_reset(void *ctx, const uint8_t *mask, const float *params, const int32_t *max_t,
              const uint8_t *one_starts, void *stream);
+
+/* HockeyEnv.reset(seed=s) with the placement drawn ON THE DEVICE, one lane per arena: replaces the reference's
+ * np_random(seed) (gymnasium.utils.seeding: Generator(PCG64(SeedSequence(seed)))), self.r_uniform
+ * (hockey_env.py:180-181) and the draws of reset (hockey_env.py:357-411), bit for bit -- the same [N,6] params and
+ * max_timesteps a host would draw with numpy and pass to hk_reset.  seeds ([N] u64, DEVICE memory like every array;
+ * a non-negative int64 array is the same bytes) holds one seed per arena, 0 <= seed < 2^64; seed=None (OS entropy)
+ * and larger seeds have no device form.
+ *
+ * hk_seeded_params writes params ([N,6] f32) and, if max_t is not NULL, max_t ([N] i32: 250 NORMAL / 80 training)
+ * for the context's mode.  one_starts ([N] u8, 0 or 1) is the puck side of NORMAL mode; NULL = each arena's stored
+ * flag as it stands (no toggle).  It touches no arena.
+ *
+ * hk_reset_seeded is hk_reset for the arenas the mask selects ([N] u8, NULL = all) with arena a's placement drawn
+ * from seeds[a].  one_starts NULL toggles the arena's flag like reset(one_starting=None) (NORMAL mode), and the
+ * toggled value is the side the placement is drawn for; given, it is that side and becomes the flag.  max_t has
+ * hk_reset's contract: NULL = mode default; given, it is range-checked on the host ([0, 65535], HK_E_INVALID and
+ * nothing changed otherwise), which copies it on `stream` and synchronises.  Without max_t the call is
+ * fire-and-forget on `stream` and legal under stream capture (two launches: the placement into context-owned
+ * scratch, then hk_reset's kernel).  Arenas outside the mask keep every word, the episode word and the one_starts
+ * flag included. */
+int hk_seeded_params(void *ctx, const uint64_t *seeds, const uint8_t *one_starts, float *params, int32_t *max_t,
+                     void *stream);
+int hk_reset_seeded(void *ctx, const uint8_t *mask, const uint64_t *seeds, const int32_t *max_t,
+                    const uint8_t *one_starts, void *stream);
 
 int hk_step(void *ctx, const hk_step_io *io, void *stream);
 
