@@ -6,6 +6,8 @@ Public surface:
                                     the reference's single-env API (hockey_amd.hockey_env)
   ArenaSnapshot, Lookahead          exact arena snapshots (VecHockeyEnv.snapshot / restore / fork) and K-way
                                     lookahead over forked arenas (hockey_amd.snapshot, hockey_amd.lookahead)
+  ValueFn, ShootingPlanner          a TD3 agent's twin-critic values Q(s, a) / V(s) on batches, and random-shooting
+                                    MPC on value-bootstrapped lookahead (hockey_amd.value, hockey_amd.planner)
 The compute path is libhockey_hip.so (csrc/, C ABI in include/hockey.h); torch only provides device
 memory and streams.
 """
@@ -25,4 +27,10 @@ def __getattr__(name):
     if name == "Lookahead":
         from .lookahead import Lookahead
         return Lookahead
+    if name == "ValueFn":
+        from .value import ValueFn
+        return ValueFn
+    if name == "ShootingPlanner":
+        from .planner import ShootingPlanner
+        return ShootingPlanner
     raise AttributeError(name)

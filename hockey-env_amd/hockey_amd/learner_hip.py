@@ -15,7 +15,8 @@ On a ``hockey_amd.td3.DevicePrioritizedRing`` the prioritized slots, importance 
 the hkl_per_* kernels (per-block float64 sums; the slots come from the Philox stream under rng="device").
 
 ``ActIO`` / ``hkl_act`` (actor inference over a bank of policies) is bound here and driven by
-``hockey_amd.policy_bank.PolicyBank``.
+``hockey_amd.policy_bank.PolicyBank``; ``ValueIO`` / ``hkl_value`` (twin-critic inference) by
+``hockey_amd.value.ValueFn``.
 
 Every call is asynchronous on torch's current stream and graph-capturable (fixed buffers, device step counters).
 There is no CPU path: construction fails loudly without the library or a GPU.
@@ -104,10 +105,19 @@ class ActIO(ctypes.Structure):
                 ("out_col", ctypes.c_int32), ("order", vp), ("counts", vp), ("offsets", vp)]
 
 
+class ValueIO(ctypes.Structure):
+    """hkl_value_io: twin-critic inference, Q(obs, act) or V(obs) = min Q(obs, actor(obs)) (hockey_amd.value)."""
+    _fields_ = [("n_rows", ctypes.c_int32), ("actor", Net), ("q", Net * 2), ("obs", vp), ("obs_ld", ctypes.c_int64),
+                ("act", vp), ("act_ld", ctypes.c_int64), ("act_low", ctypes.c_float * 4),
+                ("act_range", ctypes.c_float * 4), ("q1", vp), ("q2", vp), ("qmin", vp), ("act_out", vp),
+                ("act_out_ld", ctypes.c_int64)]
+
+
 EXPORTS = ["hkl_last_error", "hkl_pack_floats", "hkl_pack", "hkl_critic_step", "hkl_actor_step", "hkl_wgrad",
            "hkl_wgrad_pair",
            "hkl_adam", "hkl_polyak", "hkl_tanh_probe", "hkl_sample", "hkl_per_block", "hkl_per_refresh",
-           "hkl_per_push", "hkl_per_sample", "hkl_per_weights", "hkl_per_update", "hkl_act", "hkl_act_io_size"]
+           "hkl_per_push", "hkl_per_sample", "hkl_per_weights", "hkl_per_update", "hkl_act", "hkl_act_io_size", "hkl_value",
+           "hkl_value_io_size"]
 
 
 def tanh_probe(x):
@@ -145,10 +155,13 @@ def lib():
         L.hkl_per_weights.argtypes = [ctypes.POINTER(PerSampleIO), vp]
         L.hkl_per_update.argtypes = [ctypes.POINTER(PerUpdateIO), vp]
         L.hkl_act.argtypes = [ctypes.POINTER(ActIO), vp]
+        L.hkl_value.argtypes = [ctypes.POINTER(ValueIO), vp]
         if L.hkl_pack_floats() != PACK_FLOATS:
             raise _native.HockeyNativeError("libhockey_learner.so pack size differs from hockey_amd.learner_hip")
         if L.hkl_act_io_size() != ctypes.sizeof(ActIO):
             raise _native.HockeyNativeError("libhockey_learner.so hkl_act_io differs from hockey_amd.learner_hip")
+        if L.hkl_value_io_size() != ctypes.sizeof(ValueIO):
+            raise _native.HockeyNativeError("libhockey_learner.so hkl_value_io differs from hockey_amd.learner_hip")
         _lib = L
     return _lib
 

@@ -9,6 +9,11 @@ The copies are exact (hk_copy_arenas: contacts and warm-start impulses included)
 fused bots and given ``opp_inc`` -- a branch is the trajectory the live arena itself would take under those actions.
 Fused policies that draw on the device (random actions, bot phase increments without ``opp_inc``) draw from the
 WORKSPACE arena's stream, which is keyed by its own index (include/hockey.h).
+
+Over a horizon a planner can afford almost no branch ends in a goal, and ``returns`` is a few steps of the closeness
+term.  ``evaluate(..., value=vf)`` with a ``hockey_amd.value.ValueFn`` adds the terminal value: ``values`` = V(s_H) of
+player 1's observation at the end of every branch (one ``vf.v`` call on the M * K rows) and ``bootstrapped`` =
+``bootstrap(returns, dones, values, gamma)`` = returns + gamma^H V(s_H) for the branches that did not end.
 """
 import torch
 
@@ -17,10 +22,21 @@ from .vec_env import VecHockeyEnv
 
 
 class LookaheadResult:
-    __slots__ = ("rewards", "dones", "winner", "returns")
+    __slots__ = ("rewards", "dones", "winner", "returns", "values", "bootstrapped")
 
-    def __init__(self, rewards, dones, winner, returns):
+    def __init__(self, rewards, dones, winner, returns, values=None, bootstrapped=None):
         self.rewards, self.dones, self.winner, self.returns = rewards, dones, winner, returns
+        self.values, self.bootstrapped = values, bootstrapped
+
+
+def bootstrap(returns, dones, values, gamma):
+    """returns [M, K] f32, dones [H, M, K] (non-zero: done), values [M, K] f32 = V(s_H) -> [M, K] f32: a branch with
+    a done step inside the horizon keeps its return (whatever its value entry holds), every other branch gets
+    returns + gamma^H values.  Float64 arithmetic, rounded once to float32; any device."""
+    H = dones.shape[0]
+    ended = (dones != 0).any(dim=0)
+    tail = torch.where(ended, torch.zeros_like(values, dtype=torch.float64), values.to(torch.float64))
+    return (returns.to(torch.float64) + float(gamma) ** H * tail).to(torch.float32)
 
 
 class Lookahead:
@@ -49,7 +65,7 @@ class Lookahead:
     def close(self):
         self.ws.close()
 
-    def evaluate(self, src, actions, opp_inc=None, assume_valid=False):
+    def evaluate(self, src, actions, opp_inc=None, assume_valid=False, value=None):
         """src: [M] arena ids of the live env (M <= max_sources); actions: [H, M, K, 8]; opp_inc: [H, M, K, 2]
         BasicOpponent phase increments or None.  Returns a LookaheadResult of device tensors:
           rewards [H, M, K] f32, dones [H, M, K] u8   as the step kernel wrote them (done is sticky: after a branch's
@@ -57,7 +73,11 @@ class Lookahead:
           winner  [M, K] i32                          -1 / 0 / 1 at the end of the horizon
           returns [M, K] f32                          sum over t of gamma^t r_t up to AND INCLUDING the branch's first
                                                       done step (accumulated in float64): the repeated terminal
-                                                      reward of the sticky done is not counted."""
+                                                      reward of the sticky done is not counted.
+        value: a hockey_amd.value.ValueFn (or None).  With it, two more fields (None without):
+          values [M, K] f32                           V(s_H) = value.v of player 1's observation of the workspace
+                                                      arenas after the rollout
+          bootstrapped [M, K] f32                     bootstrap(returns, dones, values, gamma)"""
         H, K, ws = self.H, self.K, self.ws
         src = torch.as_tensor(src, device=self.env.device).to(torch.int64).reshape(-1)
         M = src.numel()
@@ -92,4 +112,7 @@ class Lookahead:
         before = torch.cumsum(d, dim=0) - d
         live = (before == 0).to(torch.float64)
         returns = (rewards.to(torch.float64) * live * self._disc[:, None, None]).sum(dim=0).to(torch.float32)
-        return LookaheadResult(rewards, dones, winner, returns)
+        if value is None:
+            return LookaheadResult(rewards, dones, winner, returns)
+        values = value.v(ws.observe()[0][:mk]).reshape(M, K)
+        return LookaheadResult(rewards, dones, winner, returns, values, bootstrap(returns, dones, values, self.gamma))

@@ -223,6 +223,37 @@ typedef struct {
 int hkl_act_io_size(void);
 int hkl_act(const hkl_act_io *io, void *stream);
 
+/* ---- twin-critic inference (hockey_amd/value.py) ----
+ * The clipped double-Q value of a TD3 agent outside the learner, one launch for n_rows rows:
+ *   Q mode (act given):   q_k[i] = Q_k(obs[i * obs_ld .. + 18), unscale(act[i * act_ld .. + 4)))
+ *   V mode (act == NULL): a = tanh(actor(obs[i])) as hkl_act computes it, q_k[i] = Q_k(obs[i], unscale(a)) -- the
+ *                         critic step's target path with zero noise; the action stays in registers.  act_out
+ *                         (optional) receives a in act_out[i * act_out_ld .. + 4).
+ * qmin[i] = fminf(q1[i], q2[i]).  unscale is TwinQNetwork._unscale_action with act_low / act_range, as in
+ * hkl_critic_io.  The three networks' packs are written by hkl_pack (actor n_in 18 / n_out 4, critics 22 / 1); the
+ * actor is read in V mode only.  Any of q1 / q2 / qmin / act_out may be NULL, but not all of them.
+ *
+ * No float of an output outside its n_rows entries (act_out: the rows' four columns) is written.  A row's results do
+ * not depend on the other rows or on its position (bit for bit).  Asynchronous on stream, graph-capturable, no host
+ * synchronisation; n_rows == 0 launches nothing.  HKL_E_INVALID (hkl_last_error says which): n_rows < 0, obs_ld < 18,
+ * act given with act_ld < 4, act_out given together with act or with act_out_ld < 4, a null obs, a null pack or
+ * weight pointer of a network the mode reads, all four outputs null. */
+typedef struct {
+  int32_t n_rows;
+  hkl_net actor;
+  hkl_net q[2];
+  const float *obs;
+  int64_t obs_ld;
+  const float *act;
+  int64_t act_ld;
+  float act_low[4], act_range[4];
+  float *q1, *q2, *qmin;
+  float *act_out;
+  int64_t act_out_ld;
+} hkl_value_io;
+int hkl_value_io_size(void);
+int hkl_value(const hkl_value_io *io, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
