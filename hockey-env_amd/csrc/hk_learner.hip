@@ -359,12 +359,19 @@ __device__ __forceinline__ f4 sample_noise(uint64_t seed, int64_t e, uint64_t ct
   for (int c = 0; c < 4; ++c) nz[c] = fminf(fmaxf(z[c] * scale, -clip), clip);
   return nz;
 }
-__global__ void __launch_bounds__(256) sample_kernel(hkl_sample_io io) {
+// Every learner kernel's body is a __device__ function of its io struct: the single-member kernel passes its by-value
+// argument, the grouped twin (the *_group_kernel after it) member m's struct from an array in device memory, m taken
+// from a grid dimension the body does not read.  The struct reads are wave-uniform either way.
+__device__ __forceinline__ void sample_body(const hkl_sample_io &io) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= io.batch) return;
   const uint64_t ctr = (uint64_t)*io.counter, size = (uint64_t)*io.size;
   io.idx[e] = sample_slot(io.seed, e, ctr, size);
   *reinterpret_cast<f4 *>(io.noise + e * 4) = sample_noise(io.seed, e, ctr, io.scale, io.clip);
+}
+__global__ void __launch_bounds__(256) sample_kernel(hkl_sample_io io) { sample_body(io); }
+__global__ void __launch_bounds__(256) sample_group_kernel(const hkl_sample_io *__restrict__ ios) {
+  sample_body(ios[blockIdx.y]);
 }
 
 // ------------------------------------------------------------------------------------------------ critic step
@@ -409,7 +416,7 @@ __device__ __forceinline__ void critic_one(const hkl_critic_io &io, int k, const
 }
 
 // compute_target + update_critic's forward / loss / backward for both critics (learner.py:75-136).
-__global__ void __launch_bounds__(WG, 1) critic_step_kernel(hkl_critic_io io) {
+__device__ __forceinline__ void critic_step_body(const hkl_critic_io &io) {
   __shared__ f4 sfrag[2 * 16 * 64 + 64];  // two fragment buffers + the staged bias
   __shared__ float red[4 * H];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, j = lane & 15;
@@ -461,10 +468,14 @@ __global__ void __launch_bounds__(WG, 1) critic_step_kernel(hkl_critic_io io) {
   if (threadIdx.x == 0) io.p_loss[blockIdx.x] = ls;
   if (io.sample_counter && blockIdx.x == 0 && threadIdx.x == 0) *io.sample_counter += 1;
 }
+__global__ void __launch_bounds__(WG, 1) critic_step_kernel(hkl_critic_io io) { critic_step_body(io); }
+__global__ void __launch_bounds__(WG, 1) critic_step_group_kernel(const hkl_critic_io *__restrict__ ios) {
+  critic_step_body(ios[blockIdx.y]);
+}
 
 // ------------------------------------------------------------------------------------------------ actor step
 // update_actor's forward / backward (learner.py:138-175): loss = -mean Q1(s, actor(s)) with the updated critic.
-__global__ void __launch_bounds__(WG, 1) actor_step_kernel(hkl_actor_io io) {
+__device__ __forceinline__ void actor_step_body(const hkl_actor_io &io) {
   __shared__ f4 sfrag[2 * 16 * 64 + 64];  // two fragment buffers + the staged bias
   __shared__ float red[4 * H];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, j = lane & 15;
@@ -542,6 +553,10 @@ __global__ void __launch_bounds__(WG, 1) actor_step_kernel(hkl_actor_io io) {
   const float ls = wg_scalar_sum(-qv, red, wave, lane);
   if (threadIdx.x == 0) io.p_loss[blockIdx.x] = ls;
 }
+__global__ void __launch_bounds__(WG, 1) actor_step_kernel(hkl_actor_io io) { actor_step_body(io); }
+__global__ void __launch_bounds__(WG, 1) actor_step_group_kernel(const hkl_actor_io *__restrict__ ios) {
+  actor_step_body(ios[blockIdx.y]);
+}
 
 // ------------------------------------------------------------------------------------------------ weight gradients
 // dW[o][k] = sum_j DZ[j][o] X[j][k] over one chunk of CHUNK samples, o in 128-row tiles, k in KT-wide tiles; 4 waves
@@ -559,24 +574,22 @@ struct WgJobs {
   int chunks, chunk_size;
 };
 constexpr int kWgSub = 32, kWgOt = 128, kWgPad = 4;
-// One split-K tile of dW = DZ^T X: output rows [o0, o0 + 128) x k columns [k0, k0 + KT) of job jb, summed over one
-// chunk of samples (sa / sb: this block's double-buffered LDS staging, [2][32][128 + 4] and [2][32][KT + 4]).
+// One split-K tile of dW = DZ^T X: output rows [o0, o0 + 128) x k columns [k0, k0 + KT) of one job, summed over chunk
+// `chunk` of csize samples (sa / sb: this block's double-buffered LDS staging, [2][32][128 + 4] and [2][32][KT + 4]).
 template <int KT>
-__device__ __forceinline__ void wgrad_tile(const WgJobs &jobs, int bx, int by, int bz, float (*sa)[kWgSub][kWgOt + kWgPad],
-                                           float (*sb)[kWgSub][KT + kWgPad]) {
+__device__ __forceinline__ void wgrad_tile(const WgJob &job, int bx, int by, int chunk, int csize,
+                                           float (*sa)[kWgSub][kWgOt + kWgPad], float (*sb)[kWgSub][KT + kWgPad]) {
   constexpr int SUB = kWgSub, OT = kWgOt;
   constexpr int NB = KT == 128 ? 4 : 1;  // 16-column blocks per wave
   constexpr int LA = SUB * OT / 4 / WG, LB = (SUB * KT / 4 + WG - 1) / WG;  // f4 loads per thread per sub-chunk
-  const int jb = bz / jobs.chunks, chunk = bz % jobs.chunks;
-  const float *__restrict__ dz = jobs.job[jb].dz;
-  const float *__restrict__ xs = jobs.job[jb].x;
-  float *__restrict__ slab = jobs.job[jb].slab;
-  float *__restrict__ bslab = jobs.job[jb].bslab;
-  const int ldx = jobs.job[jb].ldx;
+  const float *__restrict__ dz = job.dz;
+  const float *__restrict__ xs = job.x;
+  float *__restrict__ slab = job.slab;
+  float *__restrict__ bslab = job.bslab;
+  const int ldx = job.ldx;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, kk = lane >> 4, i = lane & 15;
   const int wo = wave >> 1, wk = wave & 1;
   const int o0 = bx * OT, k0 = by * KT;
-  const int csize = jobs.chunk_size;
   const int64_t j0 = (int64_t)chunk * csize;
   const bool bias = bslab != nullptr && by == 0;
   f4 acc[4][NB];
@@ -657,30 +670,57 @@ template <int KT>
 __global__ void __launch_bounds__(WG, 1) wgrad_kernel(WgJobs jobs) {
   __shared__ float sa[2][kWgSub][kWgOt + kWgPad];
   __shared__ float sb[2][kWgSub][KT + kWgPad];
-  wgrad_tile<KT>(jobs, blockIdx.x, blockIdx.y, blockIdx.z, sa, sb);
+  const int bz = blockIdx.z;
+  wgrad_tile<KT>(jobs.job[bz / jobs.chunks], blockIdx.x, blockIdx.y, bz % jobs.chunks, jobs.chunk_size, sa, sb);
 }
 
 // hkl_wgrad_pair: a network's dW2 tiles (k width 256) and dW1 tiles (k width 32) in one launch -- blocks
 // [0, n_wide) take the wide jobs (grid 2 x 2 x chunks per job), the rest the narrow ones (2 x 1 x chunks), so the
 // short dW1 tiles fill the SIMDs the dW2 tiles leave and one launch gap is saved.  The narrow tile's staging
 // lives inside the wide one's (same LDS as a wide-only block).
-__global__ void __launch_bounds__(WG, 1) wgrad_pair_kernel(WgJobs wide, WgJobs narrow, int n_wide) {
+// One block of the pair: jobs are read through job_of(width, j), which the single kernel answers from its by-value
+// WgJobs and the grouped one from member blockIdx.y's hkl_wgrad_job rows in device memory.
+template <class JobOf>
+__device__ __forceinline__ void wgrad_pair_body(const JobOf &job_of, int chunks_wide, int csize_wide, int chunks_narrow,
+                                                int csize_narrow, int n_wide) {
   __shared__ float sa[2][kWgSub][kWgOt + kWgPad];
   __shared__ float sb[2][kWgSub][128 + kWgPad];
   static_assert(sizeof(float[2][kWgSub][XP + kWgPad]) <= sizeof(sb), "the narrow staging fits the wide one");
   const int id = blockIdx.x;
   if (id < n_wide) {
-    wgrad_tile<128>(wide, id & 1, (id >> 1) & 1, id >> 2, sa, sb);
+    const int z = id >> 2;
+    wgrad_tile<128>(job_of(true, z / chunks_wide), id & 1, (id >> 1) & 1, z % chunks_wide, csize_wide, sa, sb);
   } else {
-    const int j = id - n_wide;
-    wgrad_tile<XP>(narrow, j & 1, 0, j >> 1, sa, reinterpret_cast<float(*)[kWgSub][XP + kWgPad]>(&sb[0][0][0]));
+    const int j = id - n_wide, z = j >> 1;
+    wgrad_tile<XP>(job_of(false, z / chunks_narrow), j & 1, 0, z % chunks_narrow, csize_narrow, sa,
+                   reinterpret_cast<float(*)[kWgSub][XP + kWgPad]>(&sb[0][0][0]));
   }
+}
+__global__ void __launch_bounds__(WG, 1) wgrad_pair_kernel(WgJobs wide, WgJobs narrow, int n_wide) {
+  wgrad_pair_body([&](bool w, int j) -> const WgJob & { return w ? wide.job[j] : narrow.job[j]; }, wide.chunks,
+                  wide.chunk_size, narrow.chunks, narrow.chunk_size, n_wide);
+}
+// member blockIdx.y's jobs: rows [m * n_jobs, (m + 1) * n_jobs) of the two device arrays
+struct WgGroup {
+  const hkl_wgrad_job *wide, *narrow;
+  int n_wide_jobs, n_narrow_jobs;
+  int chunks_wide, csize_wide, chunks_narrow, csize_narrow;
+  int n_wide;  // wide blocks per member
+};
+__global__ void __launch_bounds__(WG, 1) wgrad_pair_group_kernel(WgGroup g) {
+  const int m = blockIdx.y;
+  wgrad_pair_body(
+      [&](bool w, int j) {
+        const hkl_wgrad_job &d = w ? g.wide[m * g.n_wide_jobs + j] : g.narrow[m * g.n_narrow_jobs + j];
+        return WgJob{d.dz, d.x, d.slab, d.bias_slab, w ? 256 : XP};
+      },
+      g.chunks_wide, g.csize_wide, g.chunks_narrow, g.csize_narrow, g.n_wide);
 }
 
 // ------------------------------------------------------------------------------------------------ Adam
 // grad(e) = sum over chunks c (in order) of src[c * stride + row(e) * ld + col(e)]; then torch.optim.Adam (L2 weight
 // decay, bias-corrected moments).  step: the optimiser's step count before this update (device, advanced by pack).
-__global__ void __launch_bounds__(256) adam_kernel(hkl_adam_io io) {
+__device__ __forceinline__ void adam_body(const hkl_adam_io &io) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   int sidx = -1;
   int64_t base = 0;
@@ -773,6 +813,10 @@ __global__ void __launch_bounds__(256) adam_kernel(hkl_adam_io io) {
     }
   }
 }
+__global__ void __launch_bounds__(256) adam_kernel(hkl_adam_io io) { adam_body(io); }
+__global__ void __launch_bounds__(256) adam_group_kernel(const hkl_adam_io *__restrict__ ios) {
+  adam_body(ios[blockIdx.y]);
+}
 
 // target <- target * rho + tau * param (learner.py:214-218: mul_(rho), add_((1 - rho) * param); tau = 1 - rho
 // rounded to fp32 like the reference's scalar)
@@ -788,7 +832,7 @@ __global__ void tanh_probe_kernel(const float *x, float *y, int64_t n) {
 }
 
 // ------------------------------------------------------------------------------------------------ packing
-__global__ void __launch_bounds__(256) pack_kernel(hkl_pack_io io) {
+__device__ __forceinline__ void pack_body(const hkl_pack_io &io) {
   const hkl_net &N = io.net[blockIdx.y];
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (blockIdx.y == 0 && e == 0 && io.step) *io.step += 1;  // the optimiser step this pack follows
@@ -818,6 +862,10 @@ __global__ void __launch_bounds__(256) pack_kernel(hkl_pack_io io) {
     v = N.n_in == 22 ? N.w1[n * 22 + 18 + c] : 0.0f;
   }
   pk[e] = v;
+}
+__global__ void __launch_bounds__(256) pack_kernel(hkl_pack_io io) { pack_body(io); }
+__global__ void __launch_bounds__(256) pack_group_kernel(const hkl_pack_io *__restrict__ ios) {
+  pack_body(ios[blockIdx.z]);
 }
 
 }  // namespace hkl
@@ -929,6 +977,161 @@ int hkl_sample(const hkl_sample_io *io, void *stream) {
   hipLaunchKernelGGL(sample_kernel, dim3((unsigned)((io->batch + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *io);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? HKL_OK : fail(e, "hkl_sample");
+}
+
+// ---- grouped forms (include/hockey_learner.h): every member's struct is checked on the host copy, then one launch
+// reads the device copy.  bad_*: what is wrong with one member's struct, or nullptr.
+static bool null_net(const hkl_net &n) { return !n.w1 || !n.b1 || !n.w2 || !n.b2 || !n.w3 || !n.b3 || !n.pack; }
+static const char *bad_batch(int64_t b) { return (b <= 0 || b % CHUNK) ? "batch is not a positive multiple of 256" : nullptr; }
+static const char *bad_sample(const hkl_sample_io &io) {
+  if (const char *w = bad_batch(io.batch)) return w;
+  return (!io.counter || !io.size || !io.idx || !io.noise) ? "null counter / size / idx / noise" : nullptr;
+}
+static const char *bad_critic(const hkl_critic_io &io) {
+  if (const char *w = bad_batch(io.batch)) return w;
+  if (!io.idx || !io.ring_s || !io.ring_a || !io.ring_r || !io.ring_s2 || !io.ring_d || !io.noise)
+    return "null idx / ring column / noise";
+  if (null_net(io.target_actor) || null_net(io.target_q[0]) || null_net(io.target_q[1]) || null_net(io.q[0]) ||
+      null_net(io.q[1]))
+    return "null network pointer";
+  if (!io.x0 || !io.p_loss) return "null x0 / p_loss";
+  for (int k = 0; k < 2; ++k)
+    if (!io.h1[k] || !io.dz1[k] || !io.dz2[k] || !io.p_dw3[k] || !io.p_db3[k]) return "null h1 / dz1 / dz2 / p_dw3 / p_db3";
+  return nullptr;
+}
+static const char *bad_actor(const hkl_actor_io &io) {
+  if (const char *w = bad_batch(io.batch)) return w;
+  if (!io.idx || !io.ring_s) return "null idx / ring_s";
+  if (null_net(io.actor) || null_net(io.q1)) return "null network pointer";
+  if (!io.x0 || !io.h1 || !io.h2 || !io.dz1 || !io.dz2 || !io.p_dw3 || !io.p_db3 || !io.p_loss)
+    return "null x0 / h1 / h2 / dz1 / dz2 / p_dw3 / p_db3 / p_loss";
+  return nullptr;
+}
+static const char *bad_adam(const hkl_adam_io &io) {
+  if (io.n_seg < 1 || io.n_seg > HKL_MAX_SEG) return "n_seg outside [1, HKL_MAX_SEG]";
+  if (io.loss_src && (!io.loss_sum || !io.loss_count)) return "loss partials without loss_sum / loss_count";
+  if (!io.step) return "null step";
+  for (int s = 0; s < io.n_seg; ++s)
+    if (!io.seg[s].param || !io.seg[s].m || !io.seg[s].v || !io.seg[s].src || (io.polyak && !io.seg[s].target))
+      return "null segment pointer";
+  return nullptr;
+}
+static int bad_group(const char *who, const void *host, const void *dev, int n_members) {
+  if (n_members < 1 || n_members > HKL_GROUP_MAX)
+    snprintf(g_err, sizeof g_err, "%s: n_members %d outside [1, %d]", who, n_members, HKL_GROUP_MAX);
+  else if (!host || !dev) snprintf(g_err, sizeof g_err, "%s: null %s array", who, host ? "dev" : "host");
+  else return 0;
+  return HKL_E_INVALID;
+}
+static int bad_member(const char *who, int m, const char *what) {
+  snprintf(g_err, sizeof g_err, "%s: member %d: %s", who, m, what);
+  return HKL_E_INVALID;
+}
+static int launched(const char *who) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? HKL_OK : fail(e, who);
+}
+
+int hkl_sample_group(const hkl_sample_io *host, const hkl_sample_io *dev, int n_members, void *stream) {
+  const char *who = "hkl_sample_group";
+  if (bad_group(who, host, dev, n_members)) return HKL_E_INVALID;
+  for (int m = 0; m < n_members; ++m) {
+    if (const char *w = bad_sample(host[m])) return bad_member(who, m, w);
+    if (host[m].batch != host[0].batch) return bad_member(who, m, "batch differs from member 0's");
+  }
+  hipLaunchKernelGGL(sample_group_kernel, dim3((unsigned)(host[0].batch / 256), n_members), dim3(256), 0,
+                     (hipStream_t)stream, dev);
+  return launched(who);
+}
+
+int hkl_critic_step_group(const hkl_critic_io *host, const hkl_critic_io *dev, int n_members, void *stream) {
+  const char *who = "hkl_critic_step_group";
+  if (bad_group(who, host, dev, n_members)) return HKL_E_INVALID;
+  for (int m = 0; m < n_members; ++m) {
+    if (const char *w = bad_critic(host[m])) return bad_member(who, m, w);
+    if (host[m].batch != host[0].batch) return bad_member(who, m, "batch differs from member 0's");
+  }
+  hipLaunchKernelGGL(critic_step_group_kernel, dim3((unsigned)(host[0].batch / 64), n_members), dim3(WG), 0,
+                     (hipStream_t)stream, dev);
+  return launched(who);
+}
+
+int hkl_actor_step_group(const hkl_actor_io *host, const hkl_actor_io *dev, int n_members, void *stream) {
+  const char *who = "hkl_actor_step_group";
+  if (bad_group(who, host, dev, n_members)) return HKL_E_INVALID;
+  for (int m = 0; m < n_members; ++m) {
+    if (const char *w = bad_actor(host[m])) return bad_member(who, m, w);
+    if (host[m].batch != host[0].batch) return bad_member(who, m, "batch differs from member 0's");
+  }
+  hipLaunchKernelGGL(actor_step_group_kernel, dim3((unsigned)(host[0].batch / 64), n_members), dim3(WG), 0,
+                     (hipStream_t)stream, dev);
+  return launched(who);
+}
+
+int hkl_wgrad_pair_group(const hkl_wgrad_job *wide_host, const hkl_wgrad_job *wide_dev, int n_wide,
+                         const hkl_wgrad_job *narrow_host, const hkl_wgrad_job *narrow_dev, int n_narrow, int64_t batch,
+                         int n_members, void *stream) {
+  const char *who = "hkl_wgrad_pair_group";
+  if (bad_group(who, wide_host, wide_dev, n_members) || bad_group(who, narrow_host, narrow_dev, n_members))
+    return HKL_E_INVALID;
+  if (n_wide < 1 || n_wide > 4 || n_narrow < 1 || n_narrow > 4 || bad_batch(batch)) {
+    snprintf(g_err, sizeof g_err, "%s: n_wide / n_narrow outside [1, 4], or the batch is not a positive multiple of 256", who);
+    return HKL_E_INVALID;
+  }
+  for (int m = 0; m < n_members; ++m) {
+    for (int k = 0; k < n_wide; ++k)
+      if (const hkl_wgrad_job &j = wide_host[m * n_wide + k]; !j.dz || !j.x || !j.slab)
+        return bad_member(who, m, "null dz / x / slab of a wide job");
+    for (int k = 0; k < n_narrow; ++k)
+      if (const hkl_wgrad_job &j = narrow_host[m * n_narrow + k]; !j.dz || !j.x || !j.slab)
+        return bad_member(who, m, "null dz / x / slab of a narrow job");
+  }
+  WgGroup g{};
+  g.wide = wide_dev;
+  g.narrow = narrow_dev;
+  g.n_wide_jobs = n_wide;
+  g.n_narrow_jobs = n_narrow;
+  g.csize_wide = wg_chunk_size(n_wide, 256, batch);  // the chunking of hkl_wgrad_pair at these job counts
+  g.csize_narrow = wg_chunk_size(n_narrow, XP, batch);
+  g.chunks_wide = (int)(batch / g.csize_wide);
+  g.chunks_narrow = (int)(batch / g.csize_narrow);
+  g.n_wide = 4 * g.chunks_wide * n_wide;
+  const int nn = 2 * g.chunks_narrow * n_narrow;
+  hipLaunchKernelGGL(wgrad_pair_group_kernel, dim3((unsigned)(g.n_wide + nn), n_members), dim3(WG), 0,
+                     (hipStream_t)stream, g);
+  return launched(who);
+}
+
+int hkl_adam_group(const hkl_adam_io *host, const hkl_adam_io *dev, int n_members, void *stream) {
+  const char *who = "hkl_adam_group";
+  if (bad_group(who, host, dev, n_members)) return HKL_E_INVALID;
+  int64_t n = 0;
+  for (int m = 0; m < n_members; ++m) {
+    if (const char *w = bad_adam(host[m])) return bad_member(who, m, w);
+    if (host[m].n_seg != host[0].n_seg) return bad_member(who, m, "n_seg differs from member 0's");
+    for (int s = 0; s < host[m].n_seg; ++s)
+      if (host[m].seg[s].rows != host[0].seg[s].rows || host[m].seg[s].cols != host[0].seg[s].cols)
+        return bad_member(who, m, "a segment's rows x cols differ from member 0's");
+  }
+  for (int s = 0; s < host[0].n_seg; ++s) n += (int64_t)host[0].seg[s].rows * host[0].seg[s].cols;
+  hipLaunchKernelGGL(adam_group_kernel, dim3((unsigned)((n + 255) / 256), n_members), dim3(256), 0, (hipStream_t)stream,
+                     dev);
+  return launched(who);
+}
+
+int hkl_pack_group(const hkl_pack_io *host, const hkl_pack_io *dev, int n_nets, int n_members, void *stream) {
+  const char *who = "hkl_pack_group";
+  if (bad_group(who, host, dev, n_members)) return HKL_E_INVALID;
+  if (n_nets < 1 || n_nets > 4) {
+    snprintf(g_err, sizeof g_err, "%s: n_nets %d outside [1, 4]", who, n_nets);
+    return HKL_E_INVALID;
+  }
+  for (int m = 0; m < n_members; ++m)
+    for (int k = 0; k < n_nets; ++k)
+      if (null_net(host[m].net[k])) return bad_member(who, m, "null network pointer");
+  hipLaunchKernelGGL(pack_group_kernel, dim3((kPackFloats + 255) / 256, n_nets, n_members), dim3(256), 0,
+                     (hipStream_t)stream, dev);
+  return launched(who);
 }
 
 int hkl_tanh_probe(const float *x, float *y, int64_t n, void *stream) {

@@ -8,6 +8,9 @@ Public surface:
                                     lookahead over forked arenas (hockey_amd.snapshot, hockey_amd.lookahead)
   ValueFn, ShootingPlanner          a TD3 agent's twin-critic values Q(s, a) / V(s) on batches, and random-shooting
                                     MPC on value-bootstrapped lookahead (hockey_amd.value, hockey_amd.planner)
+  PopulationLearner, PopulationRing, train_population
+                                    up to 64 TD3 agents trained in one process on the grouped learner kernels
+                                    (hockey_amd.population)
 The compute path is libhockey_hip.so (csrc/, C ABI in include/hockey.h); torch only provides device
 memory and streams.
 """
@@ -33,4 +36,7 @@ def __getattr__(name):
     if name == "ShootingPlanner":
         from .planner import ShootingPlanner
         return ShootingPlanner
+    if name in ("PopulationLearner", "PopulationRing", "train_population"):
+        from . import population
+        return getattr(population, name)
     raise AttributeError(name)

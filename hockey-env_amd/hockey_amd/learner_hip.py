@@ -16,7 +16,8 @@ the hkl_per_* kernels (per-block float64 sums; the slots come from the Philox st
 
 ``ActIO`` / ``hkl_act`` (actor inference over a bank of policies) is bound here and driven by
 ``hockey_amd.policy_bank.PolicyBank``; ``ValueIO`` / ``hkl_value`` (twin-critic inference) by
-``hockey_amd.value.ValueFn``.
+``hockey_amd.value.ValueFn``.  The ``hkl_*_group`` forms (up to 64 independent learners per launch, each bit for bit
+its single call) are bound here and driven by ``hockey_amd.population.PopulationLearner``.
 
 Every call is asynchronous on torch's current stream and graph-capturable (fixed buffers, device step counters).
 There is no CPU path: construction fails loudly without the library or a GPU.
@@ -35,6 +36,7 @@ MAX_SEG = 12
 CHUNK = 256  # batch granularity (include/hockey_learner.h)
 XP = 32
 ACT_MAX_POLICIES = 64  # HKL_ACT_MAX_POLICIES
+GROUP_MAX = 64  # HKL_GROUP_MAX: members of one grouped learner launch (hockey_amd.population)
 ACT_PARAM_FLOATS = 256 * 18 + 256 + 256 * 256 + 256 + 4 * 256 + 4  # HKL_ACT_PARAM_FLOATS: one bank slot's weights
 
 vp = ctypes.c_void_p
@@ -83,6 +85,11 @@ class AdamIO(ctypes.Structure):
                 ("polyak_tau", ctypes.c_float)]
 
 
+class PackIO(ctypes.Structure):
+    """hkl_pack_io: up to four networks to re-pack and the optimiser step counter the pack advances."""
+    _fields_ = [("net", Net * 4), ("step", vp)]
+
+
 class Per(ctypes.Structure):
     _fields_ = [("cap", ctypes.c_int64), ("w", vp), ("size", vp), ("bsum", vp), ("bmax", vp), ("bpre", vp),
                 ("last", vp), ("bown", vp)]
@@ -117,7 +124,8 @@ EXPORTS = ["hkl_last_error", "hkl_pack_floats", "hkl_pack", "hkl_critic_step", "
            "hkl_wgrad_pair",
            "hkl_adam", "hkl_polyak", "hkl_tanh_probe", "hkl_sample", "hkl_per_block", "hkl_per_refresh",
            "hkl_per_push", "hkl_per_sample", "hkl_per_weights", "hkl_per_update", "hkl_act", "hkl_act_io_size", "hkl_value",
-           "hkl_value_io_size"]
+           "hkl_value_io_size", "hkl_sample_group", "hkl_critic_step_group", "hkl_actor_step_group",
+           "hkl_wgrad_pair_group", "hkl_adam_group", "hkl_pack_group"]
 
 
 def tanh_probe(x):
@@ -156,6 +164,14 @@ def lib():
         L.hkl_per_update.argtypes = [ctypes.POINTER(PerUpdateIO), vp]
         L.hkl_act.argtypes = [ctypes.POINTER(ActIO), vp]
         L.hkl_value.argtypes = [ctypes.POINTER(ValueIO), vp]
+        # grouped forms: (host array, the same bytes on the device, ..., n_members, stream)
+        L.hkl_sample_group.argtypes = [ctypes.POINTER(SampleIO), vp, ctypes.c_int, vp]
+        L.hkl_critic_step_group.argtypes = [ctypes.POINTER(CriticIO), vp, ctypes.c_int, vp]
+        L.hkl_actor_step_group.argtypes = [ctypes.POINTER(ActorIO), vp, ctypes.c_int, vp]
+        L.hkl_wgrad_pair_group.argtypes = [ctypes.POINTER(WgJob), vp, ctypes.c_int, ctypes.POINTER(WgJob), vp,
+                                           ctypes.c_int, ctypes.c_int64, ctypes.c_int, vp]
+        L.hkl_adam_group.argtypes = [ctypes.POINTER(AdamIO), vp, ctypes.c_int, vp]
+        L.hkl_pack_group.argtypes = [ctypes.POINTER(PackIO), vp, ctypes.c_int, ctypes.c_int, vp]
         if L.hkl_pack_floats() != PACK_FLOATS:
             raise _native.HockeyNativeError("libhockey_learner.so pack size differs from hockey_amd.learner_hip")
         if L.hkl_act_io_size() != ctypes.sizeof(ActIO):

@@ -1,0 +1,469 @@
+"""Population TD3: up to 64 independent agents trained in one process on grouped learner kernels.
+
+A seed study runs the same small job many times: one ``hockey_amd.td3.train`` per (config, seed) on 4-20 arenas at the
+reference's learner batch of 256, where the fused learner's kernels launch 4 workgroups each on a 256-CU chip.  Here
+the S members share every launch instead:
+
+* ``PopulationLearner`` -- one ``FusedLearner`` per member (flat parameter buffers, Adam state, operand packs and
+  fixed-pointer io structs, all unchanged); their structs are gathered into host arrays, uploaded once, and every call
+  of ``FusedLearner.update`` is replaced by its ``_group`` form (include/hockey_learner.h): member m runs in slice m of
+  the grid.  An update is 5 (+ 4 on actor updates) launches whatever S is, and member m's results are bit for bit
+  those of its own FusedLearner, whatever the other members are.
+* ``PopulationRing`` -- the S replay rings in one storage, filled by one ragged push per step.
+* ``train_population`` -- ``hockey_amd.td3.train`` for S members side by side: one VecHockeyEnv of S x n arenas, one
+  ``hkl_act`` launch per step through a PolicyBank, one OpponentMix, one grouped learner.
+
+What is and is not composition-independent: the LEARNER is -- its slots and target noise come from each member's own
+Philox stream (seeded by the agent's seed), its arithmetic from the member's own grid slice.  COLLECTION is not: the
+exploration noise, the random-phase actions and the opponent draws come from torch generators shared by the
+population, and the step kernel's device draws are keyed by the global arena id, so a member's trajectory depends on
+its position in the population and on who else is in it.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from .constants import Mode
+from .evaluate import reset_params
+from .noise import make_noise
+from .td3 import TD3, Learner, ReplayRing, updates_for
+
+GROUP_MAX = 64  # HKL_GROUP_MAX
+
+
+# ---------------------------------------------------------------------------------------------------- replay
+class _MemberRing(ReplayRing):
+    """Member j's slice of a PopulationRing with ReplayRing's attributes (views; the fill level is a 0-d view of
+    the population's [S] tensor).  Filled through PopulationRing.push only."""
+
+    def __init__(self, pop, j):  # noqa: super().__init__ would allocate
+        lo, hi = j * pop.cap, (j + 1) * pop.cap
+        self.cap, self.device = pop.cap, pop.device
+        self.s, self.a, self.r, self.s2, self.d = pop.s[lo:hi], pop.a[lo:hi], pop.r[lo:hi], pop.s2[lo:hi], pop.d[lo:hi]
+        self.size_t = pop.size_t[j]
+
+    size = property(lambda self: int(self.size_t))  # one host sync
+
+    def push(self, *a):
+        raise RuntimeError("a PopulationRing member is filled through PopulationRing.push")
+
+
+class PopulationRing:
+    """S uniform FIFO replay rings (hockey_amd.td3.ReplayRing) of ``capacity`` slots each in one storage
+    [S * capacity, ...] per column; fill levels and write positions live on the device ([S] int64)."""
+
+    def __init__(self, S, capacity, device="cuda:0", n_obs=18, n_act=4):
+        self.S, self.cap = int(S), int(capacity)
+        d = self.device = torch.device(device)
+        n = self.S * self.cap
+        self.s = torch.zeros((n, n_obs), device=d)
+        self.a = torch.zeros((n, n_act), device=d)
+        self.r = torch.zeros(n, device=d)
+        self.s2 = torch.zeros((n, n_obs), device=d)
+        self.d = torch.zeros(n, device=d)
+        self.size_t = torch.zeros(self.S, dtype=torch.int64, device=d)
+        self.pos_t = torch.zeros(self.S, dtype=torch.int64, device=d)
+        self._members = [_MemberRing(self, j) for j in range(self.S)]
+        self._ar = torch.arange(self.S, device=d)
+
+    def member(self, j):
+        return self._members[j]
+
+    def push(self, member_of_row, s, a, r, s2, d):
+        """Store a ragged batch: row i goes to member ``member_of_row[i]`` ([n] int64 on the device), any number of
+        rows per member (none included), at most ``capacity`` rows in all.  The contents and the wrap-around are
+        those of S ``ReplayRing.push`` calls in member order (a member's rows keep their order); the number of
+        launches does not depend on S and nothing is read back."""
+        n = int(member_of_row.shape[0])
+        if n > self.cap:
+            raise ValueError(f"push of {n} transitions exceeds the ring capacity {self.cap}")
+        if n == 0:
+            return
+        m = member_of_row.long()
+        onehot = (m[:, None] == self._ar[None, :]).to(torch.int64)  # [n, S]
+        rank = (torch.cumsum(onehot, 0) - 1).gather(1, m[:, None]).squeeze(1)  # the row's index among its member's
+        dst = m * self.cap + (self.pos_t[m] + rank) % self.cap
+        self.s[dst] = s
+        self.a[dst] = a
+        self.r[dst] = r.float()
+        self.s2[dst] = s2
+        self.d[dst] = d.float()
+        counts = onehot.sum(0)
+        self.pos_t.copy_((self.pos_t + counts) % self.cap)
+        self.size_t.copy_(torch.clamp(self.size_t + counts, max=self.cap))
+
+
+# ---------------------------------------------------------------------------------------------------- learner
+def _upload(arr, device):
+    """The bytes of a ctypes array in device memory (uint8 tensor; the allocator's alignment exceeds any struct's)."""
+    return torch.frombuffer(bytearray(arr), dtype=torch.uint8).to(device)
+
+
+class PopulationLearner:
+    """Learner updates of S = len(agents) <= 64 TD3 agents, agent j on rings[j], at batch ``batch`` in the launches
+    one agent takes (module docstring).  rng is "device" only: each member's slots and target noise come from its own
+    Philox stream, keyed by its agent's seed.  Members may differ in seed, lr_q, lr_pol, wd_*, gamma, tau_* and the
+    target-noise scale / clip; batch_size, policy_update_freq (2) and the hidden width (256) must be equal.
+
+    ``update(train_actor)`` is one grouped update, ``run(k)`` k of them with the (critic; critic + actor) pair
+    captured as a HIP graph after ``warm_pairs`` eager pairs, as hockey_amd.td3.Learner.run does (a linear chain on
+    one stream).  ``take_losses()`` returns per-member means.  On a CPU device every member gets an eager
+    ``Learner(fused=False)`` instead, so that code built on this class is testable without a GPU."""
+
+    def __init__(self, agents, rings, batch, graphs=True, warm_pairs=3):
+        self.agents, self.rings, self.B = list(agents), list(rings), int(batch)
+        S = self.S = len(self.agents)
+        if not 1 <= S <= GROUP_MAX:
+            raise ValueError(f"a population has 1 to {GROUP_MAX} members, got {S}")
+        if len(self.rings) != S:
+            raise ValueError("one ring per agent")
+        c0 = self.agents[0].cfg
+        for j, ag in enumerate(self.agents):
+            c = ag.cfg
+            if c.batch_size != c0.batch_size:
+                raise ValueError(f"member {j}: batch_size {c.batch_size} differs from member 0's {c0.batch_size}")
+            if c.policy_update_freq != 2:
+                raise ValueError(f"member {j}: policy_update_freq must be 2, got {c.policy_update_freq}")
+            if ag.actor.fc1.out_features != 256:
+                raise ValueError(f"member {j}: hidden width must be 256, got {ag.actor.fc1.out_features}")
+            if rings[j].prioritized:
+                raise ValueError(f"member {j}: prioritized replay has no grouped kernels")
+        self.device = self.agents[0].device
+        self.train_step = 0
+        self.graph, self.warm_left = None, int(warm_pairs)
+        self.members = None
+        if self.device.type != "cuda":
+            self.eager = [Learner(ag, rg, self.B, graphs=False, fused=False) for ag, rg in zip(self.agents, self.rings)]
+            self.use_graph = False
+            return
+        from . import learner_hip as LH
+
+        self.eager = None
+        self.use_graph = bool(graphs)
+        self.LH, self.L = LH, LH.lib()
+        self.members = [LH.FusedLearner(ag, rg, self.B, rng="device") for ag, rg in zip(self.agents, self.rings)]
+        self.acc = torch.zeros((S, 4), dtype=torch.float64, device=self.device)  # per member: Learner.acc
+        for j, f in enumerate(self.members):
+            f.set_loss_accumulator(self.acc[j])
+        self._gather()
+
+    def _gather(self):
+        """The members' io structs as host arrays (kept: the grouped calls check them) and their device copies."""
+        LH, S, ms = self.LH, self.S, self.members
+        h = {"sio": (LH.SampleIO * S)(*[f.sio for f in ms]), "cio": (LH.CriticIO * S)(*[f.cio for f in ms]),
+             "aio": (LH.ActorIO * S)(*[f.aio for f in ms]), "adam_a": (LH.AdamIO * S)(*[f.adam["actor"] for f in ms])}
+        for k in ("c256", "c32", "a256", "a32"):
+            n = len(ms[0].wg[k])
+            h[k] = (LH.WgJob * (S * n))(*[f.wg[k][i] for f in ms for i in range(n)])
+        # the critic's Adam folds its soft_update in on actor updates only: one array per value of the flag
+        for flag in (0, 1):
+            arr = (LH.AdamIO * S)(*[f.adam["critic"] for f in ms])
+            for io in arr:
+                io.polyak = flag
+            h["adam_c%d" % flag] = arr
+        for io in h["adam_a"]:
+            io.polyak = 1
+        pc, pa = (LH.PackIO * S)(), (LH.PackIO * S)()
+        for j, f in enumerate(ms):
+            for i, k in enumerate(("q1", "q2")):
+                pc[j].net[i] = f.nets[k].net
+            pc[j].step = f.step["critic"].data_ptr()
+            for i, k in enumerate(("actor", "target_actor", "tq1", "tq2")):
+                pa[j].net[i] = f.nets[k].net
+            pa[j].step = f.step["actor"].data_ptr()
+        h["pack_c"], h["pack_a"] = pc, pa
+        self.host = h
+        self.dev = {k: _upload(v, self.device) for k, v in h.items()}
+        self.dptr = {k: ctypes.c_void_p(v.data_ptr()) for k, v in self.dev.items()}
+
+    # ------------------------------------------------------------------ one update
+    def update(self, train_actor):
+        """FusedLearner.update(train_actor) of every member, each call in its grouped form."""
+        if self.eager is not None:
+            for lr in self.eager:
+                lr._one(bool(train_actor))
+            return
+        L, S, B, h, ck = self.L, self.S, self.B, self.host, self.LH._check
+        st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        d = self.dptr
+        ck(L.hkl_sample_group(h["sio"], d["sio"], S, st), "hkl_sample_group")
+        ck(L.hkl_critic_step_group(h["cio"], d["cio"], S, st), "hkl_critic_step_group")
+        ck(L.hkl_wgrad_pair_group(h["c256"], d["c256"], 2, h["c32"], d["c32"], 2, B, S, st), "hkl_wgrad_pair_group")
+        adam_c = "adam_c1" if train_actor else "adam_c0"
+        ck(L.hkl_adam_group(h[adam_c], d[adam_c], S, st), "hkl_adam_group")
+        ck(L.hkl_pack_group(h["pack_c"], d["pack_c"], 2, S, st), "hkl_pack_group")
+        if not train_actor:
+            return
+        ck(L.hkl_actor_step_group(h["aio"], d["aio"], S, st), "hkl_actor_step_group")
+        ck(L.hkl_wgrad_pair_group(h["a256"], d["a256"], 1, h["a32"], d["a32"], 1, B, S, st), "hkl_wgrad_pair_group")
+        ck(L.hkl_adam_group(h["adam_a"], d["adam_a"], S, st), "hkl_adam_group")
+        ck(L.hkl_pack_group(h["pack_a"], d["pack_a"], 4, S, st), "hkl_pack_group")
+
+    def _one(self):
+        self.train_step += 1
+        self.update(self.train_step % 2 == 0)
+
+    def _pair(self):
+        self.update(False)
+        self.update(True)
+
+    def _sync_steps(self):
+        for ag in self.agents:
+            ag.train_step = self.train_step
+
+    def run(self, k):
+        """k updates of every member (hockey_amd.td3.Learner.run: graph replay of update pairs after the warm-up)."""
+        k = int(k)
+        if not self.use_graph or self.train_step % 2:
+            for _ in range(k):
+                self._one()
+            return self._sync_steps()
+        pairs, rest = divmod(k, 2)
+        dev = self.device
+        for _ in range(pairs):
+            if self.graph is not None:
+                self.graph.replay()
+            elif self.warm_left > 0:  # eager warm-up pairs on a side stream (graph capture prerequisite)
+                st = torch.cuda.Stream(dev)
+                st.wait_stream(torch.cuda.current_stream(dev))
+                with torch.cuda.stream(st):
+                    self._pair()
+                torch.cuda.current_stream(dev).wait_stream(st)
+                self.warm_left -= 1
+            else:
+                self.graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.graph):
+                    self._pair()
+                self.graph.replay()  # capture records without running: this replay is the pair's update
+            self.train_step += 2
+        for _ in range(rest):
+            self._one()
+        self._sync_steps()
+
+    def take_losses(self):
+        """[(mean critic loss, mean actor loss)] per member since the last call (None without updates)."""
+        if self.eager is not None:
+            return [lr.take_losses() for lr in self.eager]
+        rows = self.acc.cpu().tolist()  # one host sync
+        self.acc.zero_()
+        return [((s[0] / s[2] if s[2] else None), (s[1] / s[3] if s[3] else None)) for s in rows]
+
+
+# ---------------------------------------------------------------------------------------------------- training
+_SHARED = ("curriculum_name", "max_steps", "train_iters", "batch_size", "policy_update_freq", "buffer_size",
+           "eval_interval")
+
+
+def _check_members(members):
+    from .opponents import CURRICULA
+
+    out = []
+    for m in members:
+        if len(m) not in (2, 3):
+            raise ValueError("members are (TD3Config, seed) or (TD3Config, seed, resume_from)")
+        out.append((m[0], int(m[1]), m[2] if len(m) == 3 else None))
+    if not 1 <= len(out) <= GROUP_MAX:
+        raise ValueError(f"a population has 1 to {GROUP_MAX} members, got {len(out)}")
+    c0 = out[0][0]
+    for j, (c, _, _) in enumerate(out):
+        if c.prioritized_replay:
+            raise ValueError(f"member {j}: prioritized_replay is not supported by train_population")
+        if c.use_self_play and any(row[3] > 0 for row in CURRICULA[c.curriculum_name]):
+            raise ValueError(f"member {j}: self-play (use_self_play with a self-play share in curriculum "
+                             f"'{c.curriculum_name}') is not supported by train_population")
+        for k in _SHARED:
+            if getattr(c, k) != getattr(c0, k):
+                raise ValueError(f"member {j}: {k} = {getattr(c, k)!r} differs from member 0's {getattr(c0, k)!r}; "
+                                 "the members of a population share it")
+    return out
+
+
+def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode.NORMAL, episode_end="max_steps",
+                     updates_per_round=None, eval_fn=None, on_step=None, env=None, replay_capacity=None, graphs=True,
+                     log=None, timing=False):
+    """``hockey_amd.td3.train`` for S = len(members) agents side by side in one process.  ``members`` is a list of
+    (TD3Config, seed) or (TD3Config, seed, resume_from); member j owns arenas [j n, (j + 1) n) of one VecHockeyEnv of
+    S * n_arenas arenas (``env``: a ready batch of that many arenas, e.g. the kernel source's host build in the CPU
+    tests) and its own slice of a PopulationRing.  Returns (agents, stats) with stats[j] shaped like ``train``'s.
+
+    * Player 1 acts through a PolicyBank of S slots with policy[i] = i // n: one ``hkl_act`` launch per step.  The
+      bank is refreshed from the members' actors after each round's updates: actors only change there.
+    * Exploration restates ``TD3.act`` per arena: each member's total_steps advances by its running arenas, its
+      annealed scale is ``TD3.noise_scale()`` of that count, and arena i of the member draws a uniform action while
+      (total_steps before the step + 1 + i) < start_steps or the whole step lies in the random phase.  The per-member
+      counts, start_steps and scales are [S] tensors on the device; there is one noise generator per distinct
+      ``noise_mode`` over that mode's arenas (unit scale, seeded by the mode's first member), multiplied by the
+      arena's scale, and it advances on every step in which one of its members is past the all-random phase.
+    * Player 2 is one OpponentMix over all arenas (seeded by member 0), so the members share ``curriculum_name``,
+      ``max_steps`` and ``train_iters`` (and batch_size, policy_update_freq, buffer_size, eval_interval).  Self-play
+      and prioritized replay are not supported: such a member raises ValueError.
+    * Resets (episode e of member j is seeded seed_j + e), ``episode_end`` ("max_steps" / "done"), the replay ratio
+      and ``eval_fn(agent_j, episodes)`` follow ``train``, per member.
+    * Updates start in the first round after which EVERY member's total_steps exceeds the batch -- a batched
+      difference from ``train``'s per-agent guard; rounds skipped that way are counted in stats[j]["skipped_rounds"].
+    * on_step(member_of_row, arena_of_row, obs, action, reward, next_obs, done, step_result) sees every stored
+      transition of a step, ragged over the members (test hook).
+
+    Collection randomness is shared: the exploration and opponent draws come from torch generators of the whole
+    population and the step kernel's device draws are keyed by the global arena id.  A member's trajectory therefore
+    depends on its position in the population and on its size; only the learner is composition-independent (module
+    docstring)."""
+    import time
+
+    from .opponents import OpponentMix
+    from .policy_bank import PolicyBank
+
+    ms = _check_members(members)
+    if episode_end not in ("max_steps", "done"):
+        raise ValueError("episode_end must be 'max_steps' or 'done'")
+    S, n = len(ms), int(n_arenas)
+    N = S * n
+    c0 = ms[0][0]
+    dev = torch.device(device)
+    planned = rounds * c0.max_steps * n
+    agents = []
+    for cfg, seed, resume in ms:
+        ag = TD3(cfg, dev, seed, max_total_steps=planned, n_envs=1)
+        if resume is not None:
+            ag.load(resume)
+        agents.append(ag)
+    own_env = env is None
+    if own_env:
+        from .vec_env import VecHockeyEnv
+
+        env = VecHockeyEnv(N, mode=mode, device=dev, policies=("external", "external"), auto_reset=False,
+                           seed=ms[0][1])
+    mix = OpponentMix(N, c0.curriculum_name, False, c0.self_play_interval, c0.self_play_pool_size, dev, ms[0][1])
+    cap = replay_capacity or max(c0.buffer_size, n * c0.max_steps)
+    ring = PopulationRing(S, cap, device=dev)
+    batch = int(c0.batch_size)
+    learner = PopulationLearner(agents, [ring.member(j) for j in range(S)], batch, graphs=graphs)
+    updates = updates_per_round if updates_per_round is not None else updates_for(c0, n, c0.max_steps, batch)
+    bank = PolicyBank(S, dev)
+    for j, ag in enumerate(agents):
+        bank.replace(j, ag.actor)
+    member_of = torch.arange(N, device=dev) // n  # [N] int64
+    policy = member_of.to(torch.int32)
+    local = (torch.arange(N, device=dev) % n).to(torch.float64)  # an arena's index inside its member
+    # one generator per noise mode over that mode's arenas (unit scale: the arena's own scale multiplies the draw)
+    modes = {}
+    for j, (cfg, seed, _) in enumerate(ms):
+        modes.setdefault(cfg.noise_mode, []).append(j)
+    gens = {}
+    for mname, js in modes.items():
+        rows = torch.cat([torch.arange(j * n, (j + 1) * n, device=dev) for j in js])
+        gens[mname] = (make_noise(mname, rows.numel(), 4, 1.0, c0.max_steps, dev, ms[js[0]][1]), rows, js)
+    start_t = torch.tensor([float(c.start_steps) for c, _, _ in ms], dtype=torch.float64, device=dev)
+    act8 = torch.zeros((N, 8), device=dev)
+    stats = [{"env_steps": 0, "updates": 0, "updates_per_round": updates, "batch": batch,
+              "replay_ratio": updates * batch / (n * c0.max_steps), "replay_capacity": cap, "critic_loss": [],
+              "actor_loss": [], "mean_reward": [], "opponents": [], "evals": [], "round_time": [],
+              "skipped_rounds": 0, "noise_scale": []} for _ in range(S)]
+    episodes, next_eval = 0, c0.eval_interval
+    stop_at_done = episode_end == "done"
+    sync = (lambda: torch.cuda.synchronize(dev)) if timing else (lambda: None)
+    for rnd in range(rounds):
+        sync()
+        t0 = time.perf_counter()
+        mix.update_schedule((episodes + 1) / (rounds * n))
+        e = np.arange(rnd * n, (rnd + 1) * n, dtype=np.int64)  # the round's episodes of one member, 0-based
+        if hasattr(env, "reset_seeded"):
+            seeds = torch.cat([torch.arange(seed + 1 + rnd * n, seed + 1 + (rnd + 1) * n) for _, seed, _ in ms])
+            obs, obs2 = (t.clone() for t in env.reset_seeded(seeds.to(env.device), one_starting=np.tile((e % 2) == 1, S)))
+        else:
+            p = np.concatenate([reset_params(n, seed + rnd * n + 1, mode, first_reset=rnd * n)[0] for _, seed, _ in ms])
+            env.reset_params(p)
+            obs, obs2 = (t.clone() for t in env.observe())
+        for g, _, _ in gens.values():
+            g.reset()
+        ep_reward = torch.zeros(N, device=dev)
+        alive = torch.ones(N, dtype=torch.bool, device=dev)
+        n_alive = [n] * S  # per member: the arenas whose episode is still running
+        round_steps = [0] * S
+        for _ in range(c0.max_steps):
+            # ---- TD3.act per member: count, random phase, annealed scale (host scalars -> [S] tensors)
+            first = [ag.total_steps + 1 for ag in agents]
+            for ag, k in zip(agents, n_alive):
+                ag.total_steps += k
+            all_random = [ag.total_steps < ag.cfg.start_steps for ag in agents]
+            for ag, rnd_phase in zip(agents, all_random):
+                if not rnd_phase:
+                    ag.current_noise_scale = ag.noise_scale()
+            scale_t = torch.tensor([ag.current_noise_scale for ag in agents], dtype=torch.float32, device=dev)
+            first_t = torch.tensor(first, dtype=torch.float64, device=dev)
+            allr_t = torch.tensor(all_random, dtype=torch.bool, device=dev)
+            a = bank.act(obs, policy)
+            noise = torch.zeros((N, 4), device=dev)
+            for g, rows, js in gens.values():
+                if not all(all_random[j] for j in js):
+                    noise[rows] = g().float()
+            a = torch.clamp(a + noise * scale_t[member_of][:, None], -1, 1)
+            if any(f < ag.cfg.start_steps for f, ag in zip(first, agents)):
+                rnd_rows = allr_t[member_of] | ((local + first_t[member_of]) < start_t[member_of])
+                a = torch.where(rnd_rows[:, None], torch.rand((N, 4), device=dev) * 2 - 1, a)
+            policy2, a2, _ = mix.select(obs2)
+            act8[:, :4] = a
+            if a2 is not None:
+                act8[:, 4:] = a2
+            res = env.step(act8, with_agent_two=True, policy2=policy2)
+            o2, r, d = res.obs.clone(), res.reward.clone(), res.done.clone()
+            for j in range(S):
+                round_steps[j] += n_alive[j]
+            if stop_at_done:  # only the transitions of episodes that were still running are stored
+                idx = torch.nonzero(alive).squeeze(1)
+                ring.push(member_of[idx], obs[idx], a[idx], r[idx], o2[idx], d[idx])
+                if on_step is not None:
+                    on_step(member_of[idx], idx, obs[idx], a[idx], r[idx], o2[idx], d[idx], res)
+                mix.register_outcomes(d & alive, r)
+                ep_reward += torch.where(alive, r, torch.zeros_like(r))
+                alive &= d == 0
+                n_alive = alive.view(S, n).sum(1).tolist()  # the step's one host sync, as train's
+                if not any(n_alive):
+                    break
+            else:
+                ring.push(member_of, obs, a, r, o2, d)
+                if on_step is not None:
+                    on_step(member_of, torch.arange(N, device=dev), obs, a, r, o2, d, res)
+                mix.register_outcomes(d, r)
+                ep_reward += r
+            obs, obs2 = o2, res.obs2.clone()
+        episodes += n
+        opp = mix.end_round()
+        mean_r = ep_reward.view(S, n).mean(1).tolist()
+        for j in range(S):
+            stats[j]["env_steps"] += round_steps[j]
+            stats[j]["mean_reward"].append(mean_r[j])
+            stats[j]["opponents"].append(opp)  # the population's counts: one mix over all arenas
+            stats[j]["noise_scale"].append(agents[j].current_noise_scale)
+        sync()
+        t1 = time.perf_counter()
+        if all(ag.total_steps > batch for ag in agents):
+            learner.run(updates)
+            for j, (cl, al) in enumerate(learner.take_losses()):
+                stats[j]["updates"] += updates
+                stats[j]["critic_loss"].append(cl)
+                if al is not None:
+                    stats[j]["actor_loss"].append(al)
+            for j, ag in enumerate(agents):  # the actors changed: refresh the acting bank
+                bank.replace(j, ag.actor)
+        else:
+            for st in stats:
+                st["skipped_rounds"] += 1
+        sync()
+        if timing:
+            for st in stats:
+                st["round_time"].append((t1 - t0, time.perf_counter() - t1))
+        if eval_fn is not None and episodes >= next_eval:
+            for j, ag in enumerate(agents):
+                stats[j]["evals"].append(eval_fn(ag, episodes))
+            next_eval = (episodes // c0.eval_interval + 1) * c0.eval_interval
+        if log:
+            log(rnd, stats)
+    if own_env:
+        env.close()
+    sizes = ring.size_t.cpu().tolist()
+    for j, ag in enumerate(agents):
+        stats[j]["replay_size"] = sizes[j]
+        stats[j]["train_step"] = ag.train_step
+    return agents, stats

@@ -134,6 +134,37 @@ typedef struct {
 } hkl_sample_io;
 int hkl_sample(const hkl_sample_io *io, void *stream);
 
+/* ---- grouped forms: n_members <= HKL_GROUP_MAX independent learners in the launch one learner takes
+ * (hockey_amd/population.py).  Member m runs in its own slice of the grid (blockIdx.y; blockIdx.z for pack) and reads
+ * its struct from an array in device memory: 64 x sizeof(hkl_critic_io) is far beyond the kernel-argument segment.
+ *
+ *  - host: the caller's host copy of the n_members structs.  Every check of the single call runs on it for every
+ *    member; in addition n_members must lie in [1, HKL_GROUP_MAX], dev must not be null, the members' batch must be
+ *    equal (a positive multiple of 256, hkl_sample_group included), every pointer the kernel dereferences
+ *    unconditionally must be non-null (the optional ones stay optional: iw, td, sample_counter, bias_slab, loss_src,
+ *    pack's step), and for hkl_adam_group n_seg and every segment's rows x cols must be equal across members (chunks,
+ *    ld, stride, lr, wd, betas, polyak may differ).  A failed check returns HKL_E_INVALID, hkl_last_error names the
+ *    call, the member and what is wrong, and nothing is launched.
+ *  - dev: the same bytes in device memory, uploaded by the caller once.  That the two agree, and that the members'
+ *    output buffers are disjoint, is the caller's contract.
+ *  - One launch per call; asynchronous on stream, graph-capturable, no host synchronisation and no copy in the call.
+ *  - Member m's results are bit for bit those of the single call on host[m], whatever the other members are: the
+ *    same kernel body runs on the same grid slice.
+ *  - hkl_wgrad_pair_group: the arrays are [n_members][n_wide] and [n_members][n_narrow]; chunking as hkl_wgrad_pair
+ *    at the same n_wide / n_narrow / batch.  hkl_pack_group packs net[0 .. n_nets) of every member.
+ *  - hkl_adam_io.polyak is part of the struct: a caller that alternates it (the critic's Adam on critic-only and on
+ *    critic + actor updates) keeps two device arrays.
+ * Prioritized replay has no grouped form: the hkl_per_* calls below are single-member. */
+#define HKL_GROUP_MAX 64
+int hkl_sample_group(const hkl_sample_io *host, const hkl_sample_io *dev, int n_members, void *stream);
+int hkl_critic_step_group(const hkl_critic_io *host, const hkl_critic_io *dev, int n_members, void *stream);
+int hkl_actor_step_group(const hkl_actor_io *host, const hkl_actor_io *dev, int n_members, void *stream);
+int hkl_wgrad_pair_group(const hkl_wgrad_job *wide_host, const hkl_wgrad_job *wide_dev, int n_wide,
+                         const hkl_wgrad_job *narrow_host, const hkl_wgrad_job *narrow_dev, int n_narrow, int64_t batch,
+                         int n_members, void *stream);
+int hkl_adam_group(const hkl_adam_io *host, const hkl_adam_io *dev, int n_members, void *stream);
+int hkl_pack_group(const hkl_pack_io *host, const hkl_pack_io *dev, int n_nets, int n_members, void *stream);
+
 /* ---- prioritized replay (rl/replay/prioritized_buffer.py) on per-block sums: csrc/hk_learner.hip ----
  * Slot i of the ring has the sanitised weight p_i = max(nan_to_num(w_i, 0, 0, 0), 1e-6f) for i < *size and 0
  * otherwise; every sum of them is taken in float64 in a fixed order.  The ring's slots are cut into blocks of

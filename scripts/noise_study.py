@@ -22,7 +22,12 @@ At the end the best checkpoint is re-evaluated on ``--final-games`` fresh placem
 Writes <out>/<protocol>_<noise>_s<seed>.json after every evaluation and the best actor's weights (reference td3
 ``policy`` layout) as <...>_best_actor.pt whenever it changes.
 
+``--population`` runs all four noises x ``--seeds`` as the members of ONE process (hockey_amd.population: grouped
+learner kernels, one env of members x arenas arenas) and writes the same per-run files; the members' collection
+randomness is then shared (train_population docstring), each member's learner stream stays its own.
+
 Usage: python scripts/noise_study.py --protocol stage2 --noise gaussian --seed 42 --out gpurun_out/r05/noise
+       python scripts/noise_study.py --protocol stage2 --population --seeds 42,43,44 --out OUT_DIR
 """
 import argparse
 import json
@@ -102,8 +107,12 @@ def main():
     ap.add_argument("--protocol", choices=["scratch", "stage1", "stage2", "sp_per"], required=True)
     ap.add_argument("--per", type=int, default=0, help="sp_per: prioritized replay on (1) / off (0)")
     ap.add_argument("--sp", type=int, default=0, help="sp_per: self-play on (1) / off (0)")
-    ap.add_argument("--noise", choices=sorted(NOISES), required=True)
+    ap.add_argument("--noise", choices=sorted(NOISES), help="the run's noise (not with --population: it runs all)")
     ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--population", action="store_true",
+                    help="all noises x --seeds as ONE process on the grouped learner kernels "
+                         "(hockey_amd.population.train_population); writes the same per-run JSON files")
+    ap.add_argument("--seeds", default="42,43,44,45,46,47,48,49", help="--population: comma-separated seeds")
     ap.add_argument("--arenas", type=int, default=20)
     ap.add_argument("--episodes", type=int, default=10_000)
     ap.add_argument("--eval-episodes", type=int, default=100)
@@ -111,28 +120,62 @@ def main():
     ap.add_argument("--learner", choices=["auto", "fused", "eager"], default="auto")
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "noise_study"))
     args = ap.parse_args()
-    cfg, resume = config(args.protocol, args.noise, bool(args.per), bool(args.sp))
+    os.makedirs(args.out, exist_ok=True)
     n = args.arenas
     rounds = args.episodes // n
-    dev = "cuda:0"
-    os.makedirs(args.out, exist_ok=True)
-    name = f"{args.protocol}_{args.noise}" if args.protocol != "sp_per" else f"sp_per_p{args.per}_sp{args.sp}"
-    stem = os.path.join(args.out, f"{name}_s{args.seed}")
-    ref = (REFERENCE_SP_PER[(bool(args.per), bool(args.sp))] if args.protocol == "sp_per"
-           else None if args.protocol == "stage1" else REFERENCE[args.noise])
-    out = {"protocol": args.protocol, "noise": args.noise if args.protocol != "sp_per" else "ou", "seed": args.seed,
-           "per": bool(cfg.prioritized_replay), "self_play": bool(cfg.use_self_play), "config": vars(cfg),
-           "resume_from": None if resume is None else os.path.relpath(resume, ROOT), "arenas": n,
-           "episodes": rounds * n, "eval_episodes": args.eval_episodes, "reference": ref, "evals": [], "best": None,
-           "deviations": deviations(args.protocol, rounds * n)}
-    t0 = time.time()
-    best = {"score": float("-inf")}
+    if args.population:
+        if args.protocol == "sp_per":
+            ap.error("--population: the sp_per protocol switches prioritized replay and self-play, which "
+                     "train_population does not support")
+        from hockey_amd.population import train_population
 
-    def dump():
-        with open(stem + ".json", "w") as f:
-            json.dump(out, f, indent=1)
+        runs = [Run(args, noise, int(seed)) for noise in sorted(NOISES) for seed in args.seeds.split(",")]
+        by_member = {(r.cfg.noise_mode, r.seed): r for r in runs}
+        members = [(r.cfg, r.seed, r.resume) if r.resume else (r.cfg, r.seed) for r in runs]
+        _, stats = train_population(members, n_arenas=n, rounds=rounds, device="cuda:0", episode_end="done",
+                                    eval_fn=lambda ag, ep: by_member[(ag.cfg.noise_mode, ag.seed)].eval_fn(ag, ep))
+        torch.cuda.synchronize()
+        for r, st in zip(runs, stats):
+            r.out["population"] = len(runs)  # collection randomness is shared by the population's members
+            r.finish(st)
+        return
+    if args.noise is None:
+        ap.error("--noise is required without --population")
+    run = Run(args, args.noise, args.seed)
+    fused = {"auto": "auto", "fused": True, "eager": False}[args.learner]
+    agent, st = train(n_arenas=n, rounds=rounds, cfg=run.cfg, device="cuda:0", seed=args.seed, eval_fn=run.eval_fn,
+                      episode_end="done", fused=fused, resume_from=run.resume)
+    torch.cuda.synchronize()
+    run.finish(st)
 
-    def eval_fn(agent, episodes):
+
+class Run:
+    """One (protocol, noise, seed) run's record: the JSON it writes after every evaluation, the best-checkpoint rule
+    and the final re-evaluation.  The single-run path drives one; --population one per member."""
+
+    def __init__(self, args, noise, seed, dev="cuda:0"):
+        self.args, self.dev, self.seed = args, dev, seed
+        self.cfg, self.resume = config(args.protocol, noise, bool(args.per), bool(args.sp))
+        cfg, resume, n = self.cfg, self.resume, args.arenas
+        rounds = args.episodes // n
+        name = f"{args.protocol}_{noise}" if args.protocol != "sp_per" else f"sp_per_p{args.per}_sp{args.sp}"
+        self.stem = os.path.join(args.out, f"{name}_s{seed}")
+        ref = (REFERENCE_SP_PER[(bool(args.per), bool(args.sp))] if args.protocol == "sp_per"
+               else None if args.protocol == "stage1" else REFERENCE[noise])
+        self.out = {"protocol": args.protocol, "noise": noise if args.protocol != "sp_per" else "ou", "seed": seed,
+                    "per": bool(cfg.prioritized_replay), "self_play": bool(cfg.use_self_play), "config": vars(cfg),
+                    "resume_from": None if resume is None else os.path.relpath(resume, ROOT), "arenas": n,
+                    "episodes": rounds * n, "eval_episodes": args.eval_episodes, "reference": ref, "evals": [],
+                    "best": None, "deviations": deviations(args.protocol, rounds * n)}
+        self.t0 = time.time()
+        self.best = {"score": float("-inf")}
+
+    def dump(self):
+        with open(self.stem + ".json", "w") as f:
+            json.dump(self.out, f, indent=1)
+
+    def eval_fn(self, agent, episodes):
+        args, dev, best, out = self.args, self.dev, self.best, self.out
         agent.actor.eval()
         s = evaluate(agent.actor, episodes=args.eval_episodes, seed=agent.seed, weak_opponent=False, device=dev)
         w = evaluate(agent.actor, episodes=args.eval_episodes, seed=agent.seed, weak_opponent=True, device=dev)
@@ -140,37 +183,35 @@ def main():
         score = min(s["win"], w["win"])  # rl/training/train.py:228
         rec = {"episode": episodes, "updates": agent.train_step, "wr_strong": s["win"], "wr_weak": w["win"],
                "r_strong": s["mean_return"], "r_weak": w["mean_return"], "score": score,
-               "noise_scale": agent.current_noise_scale, "wall_s": round(time.time() - t0, 1)}
+               "noise_scale": agent.current_noise_scale, "wall_s": round(time.time() - self.t0, 1)}
         if score > best["score"] + 0.01:  # rl/utils/model_manager.py:15-23
             best.update(score=score, state={k: v.detach().clone() for k, v in agent.actor.state_dict().items()})
             out["best"] = dict(rec)
-            torch.save({"policy": {k: v.cpu() for k, v in best["state"].items()}}, stem + "_best_actor.pt")
+            torch.save({"policy": {k: v.cpu() for k, v in best["state"].items()}}, self.stem + "_best_actor.pt")
             rec["new_best"] = True
         out["evals"].append(rec)
-        dump()
+        self.dump()
         print(json.dumps(rec), flush=True)
         return rec
 
-    fused = {"auto": "auto", "fused": True, "eager": False}[args.learner]
-    agent, st = train(n_arenas=n, rounds=rounds, cfg=cfg, device=dev, seed=args.seed, eval_fn=eval_fn,
-                      episode_end="done", fused=fused, resume_from=resume)
-    torch.cuda.synchronize()
-    out.update(updates=st["updates"], env_steps=st["env_steps"], train_wall_s=round(time.time() - t0, 1))
-    if "state" in best:
-        actor = Actor().to(dev)
-        actor.load_state_dict(best["state"])
-        actor.eval()
-        fin = {}
-        for opp in ("strong", "weak"):
-            r = evaluate(actor, episodes=args.final_games, seed=100_000, weak_opponent=opp == "weak", device=dev)
-            fin[f"wr_{opp}"], fin[f"r_{opp}"] = r["win"], r["mean_return"]
-            fin[f"draw_{opp}"], fin[f"len_{opp}"] = r["draw"], r["mean_length"]
-        fin["games"] = args.final_games
-        out["final_eval"] = fin
-    out["wall_s"] = round(time.time() - t0, 1)
-    dump()
-    print(json.dumps({k: out.get(k) for k in ("protocol", "noise", "seed", "best", "final_eval", "wall_s")}),
-          flush=True)
+    def finish(self, st):
+        args, dev, best, out = self.args, self.dev, self.best, self.out
+        out.update(updates=st["updates"], env_steps=st["env_steps"], train_wall_s=round(time.time() - self.t0, 1))
+        if "state" in best:
+            actor = Actor().to(dev)
+            actor.load_state_dict(best["state"])
+            actor.eval()
+            fin = {}
+            for opp in ("strong", "weak"):
+                r = evaluate(actor, episodes=args.final_games, seed=100_000, weak_opponent=opp == "weak", device=dev)
+                fin[f"wr_{opp}"], fin[f"r_{opp}"] = r["win"], r["mean_return"]
+                fin[f"draw_{opp}"], fin[f"len_{opp}"] = r["draw"], r["mean_length"]
+            fin["games"] = args.final_games
+            out["final_eval"] = fin
+        out["wall_s"] = round(time.time() - self.t0, 1)
+        self.dump()
+        print(json.dumps({k: out.get(k) for k in ("protocol", "noise", "seed", "best", "final_eval", "wall_s")}),
+              flush=True)
 
 
 if __name__ == "__main__":
