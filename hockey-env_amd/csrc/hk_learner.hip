@@ -13,7 +13,8 @@
 //                 soft_update (:196-218) folded in;
 //   pack          re-lays the changed weights out for the MFMA operands (polyak: soft_update as its own launch).
 //   per_*         prioritized replay on per-block float64 sums: slots, importance weights, the priority write-back and
-//                 the push rule without a pass over the ring (after the C ABI of the stages above).
+//                 the push rule without a pass over the ring (after the C ABI of the stages above); their *_group
+//                 forms run up to 64 rings per launch, the push with its sizes read on the device.
 //   act           acting: the actor forward of actor_step over a bank of policies, a different one per row, the rows
 //                 grouped by policy on the device (near the end of this file).
 //   value         twin-critic inference: Q_k(s, a), or V(s) = min Q_k(s, actor(s)) with the action kept in registers
@@ -1227,16 +1228,27 @@ __device__ __forceinline__ void per_block_refresh(const hkl_per &P, int64_t blk,
   if (lane == 0) P.bmax[blk] = mx;
 }
 
+// The bodies below follow the learner kernels' rule (sample_body): a __device__ function of the member's struct, called
+// by the single-member kernel on its by-value argument and by the *_group_kernel on member blockIdx.y's struct in device
+// memory.  No body reads blockIdx.y, so member m computes what the single call computes, in the same order.
+
 // blocks b0 .. b0 + nb - 1, one wave each
 __global__ void __launch_bounds__(256) per_refresh_kernel(hkl_per P, int64_t b0, int64_t nb, int64_t size_arg) {
   const int64_t v = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (v >= nb) return;
   per_block_refresh(P, b0 + v, threadIdx.x & 63, per_size(P, size_arg));
 }
+// every block of every member (equal cap: nblk blocks each)
+__global__ void __launch_bounds__(256) per_refresh_group_kernel(const hkl_per *__restrict__ pers, int64_t nblk) {
+  const int64_t v = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (v >= nblk) return;
+  const hkl_per &P = pers[blockIdx.y];
+  per_block_refresh(P, v, threadIdx.x & 63, per_size(P, -1));
+}
 
 // bpre = inclusive prefix of bsum: one workgroup of 16 waves; a wave fetches eight rounds of 64 entries at a time (the
 // loads, not the additions, bound this kernel) and scans them in order
-__global__ void __launch_bounds__(1024) per_prefix_kernel(hkl_per P, int64_t nblk) {
+__device__ __forceinline__ void per_prefix_body(const hkl_per &P, int64_t nblk) {
   __shared__ double tot[16];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int64_t seg = ((nblk + 16 * 64 - 1) / (16 * 64)) * 64;  // entries per wave, a multiple of 64
@@ -1282,9 +1294,13 @@ __global__ void __launch_bounds__(1024) per_prefix_kernel(hkl_per P, int64_t nbl
     }
   }
 }
+__global__ void __launch_bounds__(1024) per_prefix_kernel(hkl_per P, int64_t nblk) { per_prefix_body(P, nblk); }
+__global__ void __launch_bounds__(1024) per_prefix_group_kernel(const hkl_per_sample_io *__restrict__ ios, int64_t nblk) {
+  per_prefix_body(ios[blockIdx.y].per, nblk);
+}
 
 // one wave per sample
-__global__ void __launch_bounds__(256) per_sample_kernel(hkl_per_sample_io io, int64_t nblk) {
+__device__ __forceinline__ void per_sample_body(const hkl_per_sample_io &io, int64_t nblk) {
   const int lane = threadIdx.x & 63;
   const int64_t e = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (e >= io.batch) return;
@@ -1351,6 +1367,10 @@ __global__ void __launch_bounds__(256) per_sample_kernel(hkl_per_sample_io io, i
     if (io.noise) *reinterpret_cast<f4 *>(io.noise + e * 4) = sample_noise(io.seed, e, ctr, io.scale, io.clip);
   }
 }
+__global__ void __launch_bounds__(256) per_sample_kernel(hkl_per_sample_io io, int64_t nblk) { per_sample_body(io, nblk); }
+__global__ void __launch_bounds__(256) per_sample_group_kernel(const hkl_per_sample_io *__restrict__ ios, int64_t nblk) {
+  per_sample_body(ios[blockIdx.y], nblk);
+}
 
 // importance weights of the slots idx[B] (learner.py:199-210), float64 inside.  Every workgroup takes the whole
 // batch's sum of raw weights itself -- thread j the samples j, j + 1024, ... in order, the 1024 partials met in a fixed
@@ -1360,8 +1380,8 @@ __global__ void __launch_bounds__(256) per_sample_kernel(hkl_per_sample_io io, i
 __device__ __forceinline__ float per_raw(const hkl_per &P, int64_t s) {
   return P.w[s < 0 ? 0 : (s >= P.cap ? P.cap - 1 : s)];
 }
-__global__ void __launch_bounds__(1024) per_iw_kernel(hkl_per P, const int64_t *idx, float *iw, int64_t batch,
-                                                      double beta) {
+__device__ __forceinline__ void per_iw_body(const hkl_per &P, const int64_t *idx, float *iw, int64_t batch,
+                                            double beta) {
   __shared__ double red[1024];
   __shared__ float rmin[1024], rmax[1024];
   const int tid = threadIdx.x;
@@ -1398,9 +1418,19 @@ __global__ void __launch_bounds__(1024) per_iw_kernel(hkl_per P, const int64_t *
   const int64_t e = (int64_t)blockIdx.x * 1024 + tid;
   if (e < batch) iw[e] = (float)(pow(1.0 / (((double)per_raw(P, idx[e]) / sum) * size), beta) / top);
 }
+__global__ void __launch_bounds__(1024) per_iw_kernel(hkl_per P, const int64_t *idx, float *iw, int64_t batch,
+                                                      double beta) {
+  per_iw_body(P, idx, iw, batch, beta);
+}
+// a member without iw takes no weights, as hkl_per_sample launches none for it: its workgroups leave together
+__global__ void __launch_bounds__(1024) per_iw_group_kernel(const hkl_per_sample_io *__restrict__ ios) {
+  const hkl_per_sample_io &io = ios[blockIdx.y];
+  if (!io.iw) return;
+  per_iw_body(io.per, io.idx, io.iw, io.batch, io.beta);
+}
 
 // write-back, pass 1: the last position of every slot (and one position per touched block) by integer maxima
-__global__ void __launch_bounds__(256) per_mark_kernel(hkl_per_update_io io) {
+__device__ __forceinline__ void per_mark_body(const hkl_per_update_io &io) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= io.batch) return;
   const int64_t s = io.idx[e];
@@ -1408,8 +1438,12 @@ __global__ void __launch_bounds__(256) per_mark_kernel(hkl_per_update_io io) {
   atomicMax(io.per.last + s, (int)e + 1);
   atomicMax(io.per.bown + s / PER_BLOCK, (int)e + 1);
 }
+__global__ void __launch_bounds__(256) per_mark_kernel(hkl_per_update_io io) { per_mark_body(io); }
+__global__ void __launch_bounds__(256) per_mark_group_kernel(const hkl_per_update_io *__restrict__ ios) {
+  per_mark_body(ios[blockIdx.y]);
+}
 // pass 2: only a slot's last position writes, and clears the slot's word
-__global__ void __launch_bounds__(256) per_write_kernel(hkl_per_update_io io) {
+__device__ __forceinline__ void per_write_body(const hkl_per_update_io &io) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= io.batch) return;
   const int64_t s = io.idx[e];
@@ -1419,8 +1453,12 @@ __global__ void __launch_bounds__(256) per_write_kernel(hkl_per_update_io io) {
   io.per.w[s] = td < 1e-6f ? 1e-6f : (td > 1e6f ? 1e6f : td);  // NaN stays, as np.clip
   __hip_atomic_store(io.per.last + s, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+__global__ void __launch_bounds__(256) per_write_kernel(hkl_per_update_io io) { per_write_body(io); }
+__global__ void __launch_bounds__(256) per_write_group_kernel(const hkl_per_update_io *__restrict__ ios) {
+  per_write_body(ios[blockIdx.y]);
+}
 // pass 3: one wave per position; the one a touched block recorded recomputes it and clears the block's word
-__global__ void __launch_bounds__(256) per_touch_kernel(hkl_per_update_io io) {
+__device__ __forceinline__ void per_touch_body(const hkl_per_update_io &io) {
   const int64_t e = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (e >= io.batch) return;
   const int64_t s = io.idx[e];
@@ -1430,10 +1468,14 @@ __global__ void __launch_bounds__(256) per_touch_kernel(hkl_per_update_io io) {
   per_block_refresh(io.per, blk, threadIdx.x & 63, per_size(io.per, -1));
   if ((threadIdx.x & 63) == 0) __hip_atomic_store(io.per.bown + blk, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+__global__ void __launch_bounds__(256) per_touch_kernel(hkl_per_update_io io) { per_touch_body(io); }
+__global__ void __launch_bounds__(256) per_touch_group_kernel(const hkl_per_update_io *__restrict__ ios) {
+  per_touch_body(ios[blockIdx.y]);
+}
 
 // PrioritizedRing._before_push: max(w[0 : size_after]) from bmax over the full blocks and a scan of the ragged one,
 // stored to the n pushed slots
-__global__ void __launch_bounds__(1024) per_push_kernel(hkl_per P, int64_t pos, int64_t n, int64_t size_after) {
+__device__ __forceinline__ void per_push_body(const hkl_per &P, int64_t pos, int64_t n, int64_t size_after) {
   __shared__ float red[1024];
   const int tid = threadIdx.x;
   const int64_t nfull = size_after / PER_BLOCK;
@@ -1452,6 +1494,58 @@ __global__ void __launch_bounds__(1024) per_push_kernel(hkl_per P, int64_t pos, 
     if (s >= P.cap) s -= P.cap;
     P.w[s] = top;
   }
+}
+__global__ void __launch_bounds__(1024) per_push_kernel(hkl_per P, int64_t pos, int64_t n, int64_t size_after) {
+  per_push_body(P, pos, n, size_after);
+}
+
+// The grouped push reads member m's (pos, n, size_after) from device memory.  What the host checks in hkl_per_push is
+// the caller's contract here; values outside it are made harmless on the device instead: a count is cut to
+// [0, max_n] (max_n <= cap), the fill level to [0, cap], and a member whose pos lies outside the ring is skipped, so
+// that no store or load leaves the member's arrays whatever the three arrays hold.
+struct PushArgs {
+  int64_t pos, n, size_after;
+};
+__device__ __forceinline__ PushArgs per_push_args(const hkl_per &P, const int64_t *pos, const int64_t *n,
+                                                  const int64_t *size_after, int64_t max_n) {
+  const int m = blockIdx.y;
+  PushArgs a{pos[m], n[m], size_after[m]};
+  a.n = a.n > max_n ? max_n : a.n;
+  if (a.pos < 0 || a.pos >= P.cap) a.n = 0;
+  a.size_after = a.size_after < 0 ? 0 : (a.size_after > P.cap ? P.cap : a.size_after);
+  return a;
+}
+__global__ void __launch_bounds__(1024) per_push_group_kernel(const hkl_per *__restrict__ pers, const int64_t *pos,
+                                                              const int64_t *n, const int64_t *size_after,
+                                                              int64_t max_n) {
+  const hkl_per &P = pers[blockIdx.y];
+  const PushArgs a = per_push_args(P, pos, n, size_after, max_n);
+  if (a.n <= 0) return;  // the whole workgroup: nothing is stored for this member
+  per_push_body(P, a.pos, a.n, a.size_after);
+}
+// hkl_per_push's two refreshes in one grid: waves [0, n_head) take the blocks of the head slots pos .. pos + head - 1,
+// waves [n_head, n_head + n_tail) those of the wrapped tail 0 .. n - head - 1; n_head / n_tail are the host's bounds
+// for a push of max_n slots, and a wave past its member's own ranges exits.
+__global__ void __launch_bounds__(256) per_push_refresh_group_kernel(const hkl_per *__restrict__ pers,
+                                                                     const int64_t *pos, const int64_t *n,
+                                                                     const int64_t *size_after, int64_t max_n,
+                                                                     int64_t n_head, int64_t n_tail) {
+  const int64_t v = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (v >= n_head + n_tail) return;
+  const hkl_per &P = pers[blockIdx.y];
+  const PushArgs a = per_push_args(P, pos, n, size_after, max_n);
+  if (a.n <= 0) return;
+  const int64_t head = P.cap - a.pos < a.n ? P.cap - a.pos : a.n;
+  int64_t blk;
+  if (v < n_head) {
+    const int64_t b0 = a.pos / PER_BLOCK;
+    blk = b0 + v;
+    if (blk > (a.pos + head - 1) / PER_BLOCK) return;
+  } else {
+    blk = v - n_head;
+    if (head >= a.n || blk > (a.n - head - 1) / PER_BLOCK) return;
+  }
+  per_block_refresh(P, blk, threadIdx.x & 63, per_size(P, a.size_after));
 }
 
 }  // namespace hkl
@@ -1524,6 +1618,124 @@ int hkl_per_update(const hkl_per_update_io *io, void *stream) {
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? HKL_OK : fail(e, "hkl_per_update");
 }
+
+// ---- grouped forms (include/hockey_learner.h): the single calls' checks on every member of the host copy, then the
+// single calls' launches with the member in blockIdx.y.  bad_per*: what is wrong with one member, or nullptr.
+static const char *bad_per(const hkl_per &p) {
+  if (p.cap <= 0) return "cap is not positive";
+  if (!p.w || !p.size || !p.bsum || !p.bmax || !p.bpre || !p.last || !p.bown)
+    return "null w / size / bsum / bmax / bpre / last / bown";
+  // per_load reads a lane's sub-chunk as four float4: the single ring's allocation is aligned, a slice of a shared
+  // storage has to be placed so
+  return ((uintptr_t)p.w % 16) ? "w is not 16-byte aligned" : nullptr;
+}
+static const char *bad_per_iw(const hkl_per_sample_io &io) {
+  if (const char *w = bad_per(io.per)) return w;
+  if (io.batch <= 0 || io.batch >= ((int64_t)1 << 31)) return "batch outside [1, 2^31)";
+  return io.idx ? nullptr : "null idx";
+}
+static const char *bad_per_update(const hkl_per_update_io &io) {
+  if (const char *w = bad_per(io.per)) return w;
+  if (io.batch <= 0 || io.batch >= ((int64_t)1 << 31)) return "batch outside [1, 2^31)";
+  return (io.idx && io.td) ? nullptr : "null idx / td";
+}
+// the members' grids agree: one cap (so one block count) and one batch
+#define HKL_PER_SAME(field, what) \
+  if (host[m].field != host[0].field) return bad_member(who, m, what " differs from member 0's")
+
+int hkl_per_refresh_group(const hkl_per *host, const hkl_per *dev, int n_members, void *stream) {
+  const char *who = "hkl_per_refresh_group";
+  if (bad_group(who, host, dev, n_members)) return HKL_E_INVALID;
+  for (int m = 0; m < n_members; ++m) {
+    if (const char *w = bad_per(host[m])) return bad_member(who, m, w);
+    HKL_PER_SAME(cap, "cap");
+  }
+  const int64_t nblk = per_nblk(&host[0]);
+  hipLaunchKernelGGL(hkl::per_refresh_group_kernel, dim3((unsigned)((nblk + 3) / 4), n_members), dim3(256), 0,
+                     (hipStream_t)stream, dev, nblk);
+  return launched(who);
+}
+
+int hkl_per_push_group(const hkl_per *host, const hkl_per *dev, const int64_t *pos, const int64_t *n,
+                       const int64_t *size_after, int64_t max_n, int n_members, void *stream) {
+  const char *who = "hkl_per_push_group";
+  if (bad_group(who, host, dev, n_members)) return HKL_E_INVALID;
+  for (int m = 0; m < n_members; ++m) {
+    if (const char *w = bad_per(host[m])) return bad_member(who, m, w);
+    HKL_PER_SAME(cap, "cap");
+  }
+  if (!pos || !n || !size_after) {
+    snprintf(g_err, sizeof g_err, "%s: null pos / n / size_after array", who);
+    return HKL_E_INVALID;
+  }
+  if (max_n < 1 || max_n > host[0].cap) {
+    snprintf(g_err, sizeof g_err, "%s: max_n %lld outside [1, cap = %lld]", who, (long long)max_n,
+             (long long)host[0].cap);
+    return HKL_E_INVALID;
+  }
+  const hipStream_t st = (hipStream_t)stream;
+  // the blocks a push of max_n slots can cover: a head that starts anywhere in a block, a tail that starts at slot 0
+  const int64_t nblk = per_nblk(&host[0]);
+  int64_t n_head = (max_n + HKL_PER_BLOCK - 2) / HKL_PER_BLOCK + 1, n_tail = (max_n - 1 + HKL_PER_BLOCK - 1) / HKL_PER_BLOCK;
+  n_head = n_head < nblk ? n_head : nblk;
+  n_tail = n_tail < nblk ? n_tail : nblk;
+  hipLaunchKernelGGL(hkl::per_push_group_kernel, dim3(1, n_members), dim3(1024), 0, st, dev, pos, n, size_after, max_n);
+  hipLaunchKernelGGL(hkl::per_push_refresh_group_kernel, dim3((unsigned)((n_head + n_tail + 3) / 4), n_members),
+                     dim3(256), 0, st, dev, pos, n, size_after, max_n, n_head, n_tail);
+  return launched(who);
+}
+
+int hkl_per_weights_group(const hkl_per_sample_io *host, const hkl_per_sample_io *dev, int n_members, void *stream) {
+  const char *who = "hkl_per_weights_group";
+  if (bad_group(who, host, dev, n_members)) return HKL_E_INVALID;
+  for (int m = 0; m < n_members; ++m) {
+    if (const char *w = bad_per_iw(host[m])) return bad_member(who, m, w);
+    if (!host[m].iw) return bad_member(who, m, "null iw");
+    HKL_PER_SAME(per.cap, "cap");
+    HKL_PER_SAME(batch, "batch");
+  }
+  hipLaunchKernelGGL(hkl::per_iw_group_kernel, dim3((unsigned)((host[0].batch + 1023) / 1024), n_members), dim3(1024),
+                     0, (hipStream_t)stream, dev);
+  return launched(who);
+}
+
+int hkl_per_sample_group(const hkl_per_sample_io *host, const hkl_per_sample_io *dev, int n_members, void *stream) {
+  const char *who = "hkl_per_sample_group";
+  if (bad_group(who, host, dev, n_members)) return HKL_E_INVALID;
+  for (int m = 0; m < n_members; ++m) {
+    if (const char *w = bad_per_iw(host[m])) return bad_member(who, m, w);
+    if (!host[m].u && !host[m].counter) return bad_member(who, m, "null u and null counter");
+    HKL_PER_SAME(per.cap, "cap");
+    HKL_PER_SAME(batch, "batch");
+  }
+  const hipStream_t st = (hipStream_t)stream;
+  const int64_t nblk = per_nblk(&host[0].per), batch = host[0].batch;
+  hipLaunchKernelGGL(hkl::per_prefix_group_kernel, dim3(1, n_members), dim3(1024), 0, st, dev, nblk);
+  hipLaunchKernelGGL(hkl::per_sample_group_kernel, dim3((unsigned)((batch + 3) / 4), n_members), dim3(256), 0, st, dev,
+                     nblk);
+  // always launched, so that the launch count does not depend on the members: one without iw leaves at once
+  hipLaunchKernelGGL(hkl::per_iw_group_kernel, dim3((unsigned)((batch + 1023) / 1024), n_members), dim3(1024), 0, st,
+                     dev);
+  return launched(who);
+}
+
+int hkl_per_update_group(const hkl_per_update_io *host, const hkl_per_update_io *dev, int n_members, void *stream) {
+  const char *who = "hkl_per_update_group";
+  if (bad_group(who, host, dev, n_members)) return HKL_E_INVALID;
+  for (int m = 0; m < n_members; ++m) {
+    if (const char *w = bad_per_update(host[m])) return bad_member(who, m, w);
+    HKL_PER_SAME(per.cap, "cap");
+    HKL_PER_SAME(batch, "batch");
+  }
+  const hipStream_t st = (hipStream_t)stream;
+  const int64_t batch = host[0].batch;
+  const dim3 g((unsigned)((batch + 255) / 256), n_members);
+  hipLaunchKernelGGL(hkl::per_mark_group_kernel, g, dim3(256), 0, st, dev);
+  hipLaunchKernelGGL(hkl::per_write_group_kernel, g, dim3(256), 0, st, dev);
+  hipLaunchKernelGGL(hkl::per_touch_group_kernel, dim3((unsigned)((batch + 3) / 4), n_members), dim3(256), 0, st, dev);
+  return launched(who);
+}
+#undef HKL_PER_SAME
 
 }  // extern "C"
 

@@ -17,7 +17,8 @@ the hkl_per_* kernels (per-block float64 sums; the slots come from the Philox st
 ``ActIO`` / ``hkl_act`` (actor inference over a bank of policies) is bound here and driven by
 ``hockey_amd.policy_bank.PolicyBank``; ``ValueIO`` / ``hkl_value`` (twin-critic inference) by
 ``hockey_amd.value.ValueFn``.  The ``hkl_*_group`` forms (up to 64 independent learners per launch, each bit for bit
-its single call) are bound here and driven by ``hockey_amd.population.PopulationLearner``.
+its single call), ``hkl_per_*_group`` among them, are bound here and driven by
+``hockey_amd.population.PopulationLearner`` and ``PopulationPrioritizedRing``.
 
 Every call is asynchronous on torch's current stream and graph-capturable (fixed buffers, device step counters).
 There is no CPU path: construction fails loudly without the library or a GPU.
@@ -125,7 +126,8 @@ EXPORTS = ["hkl_last_error", "hkl_pack_floats", "hkl_pack", "hkl_critic_step", "
            "hkl_adam", "hkl_polyak", "hkl_tanh_probe", "hkl_sample", "hkl_per_block", "hkl_per_refresh",
            "hkl_per_push", "hkl_per_sample", "hkl_per_weights", "hkl_per_update", "hkl_act", "hkl_act_io_size", "hkl_value",
            "hkl_value_io_size", "hkl_sample_group", "hkl_critic_step_group", "hkl_actor_step_group",
-           "hkl_wgrad_pair_group", "hkl_adam_group", "hkl_pack_group"]
+           "hkl_wgrad_pair_group", "hkl_adam_group", "hkl_pack_group", "hkl_per_sample_group",
+           "hkl_per_weights_group", "hkl_per_update_group", "hkl_per_refresh_group", "hkl_per_push_group"]
 
 
 def tanh_probe(x):
@@ -172,6 +174,12 @@ def lib():
                                            ctypes.c_int, ctypes.c_int64, ctypes.c_int, vp]
         L.hkl_adam_group.argtypes = [ctypes.POINTER(AdamIO), vp, ctypes.c_int, vp]
         L.hkl_pack_group.argtypes = [ctypes.POINTER(PackIO), vp, ctypes.c_int, ctypes.c_int, vp]
+        L.hkl_per_sample_group.argtypes = [ctypes.POINTER(PerSampleIO), vp, ctypes.c_int, vp]
+        L.hkl_per_weights_group.argtypes = [ctypes.POINTER(PerSampleIO), vp, ctypes.c_int, vp]
+        L.hkl_per_update_group.argtypes = [ctypes.POINTER(PerUpdateIO), vp, ctypes.c_int, vp]
+        L.hkl_per_refresh_group.argtypes = [ctypes.POINTER(Per), vp, ctypes.c_int, vp]
+        # (host, dev, pos, n, size_after: device int64[n_members], max_n, n_members, stream)
+        L.hkl_per_push_group.argtypes = [ctypes.POINTER(Per), vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int, vp]
         if L.hkl_pack_floats() != PACK_FLOATS:
             raise _native.HockeyNativeError("libhockey_learner.so pack size differs from hockey_amd.learner_hip")
         if L.hkl_act_io_size() != ctypes.sizeof(ActIO):

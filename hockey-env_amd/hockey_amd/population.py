@@ -8,8 +8,11 @@ the S members share every launch instead:
   fixed-pointer io structs, all unchanged); their structs are gathered into host arrays, uploaded once, and every call
   of ``FusedLearner.update`` is replaced by its ``_group`` form (include/hockey_learner.h): member m runs in slice m of
   the grid.  An update is 5 (+ 4 on actor updates) launches whatever S is, and member m's results are bit for bit
-  those of its own FusedLearner, whatever the other members are.
-* ``PopulationRing`` -- the S replay rings in one storage, filled by one ragged push per step.
+  those of its own FusedLearner, whatever the other members are.  Members with prioritized replay draw through
+  ``hkl_per_sample_group`` and write their priorities back through ``hkl_per_update_group`` (three launches each):
+  an all-prioritized update is 10 (+ 4) launches, a mixed one 11 (+ 4).
+* ``PopulationRing`` -- the S replay rings in one storage, filled by one ragged push per step;
+  ``PopulationPrioritizedRing`` adds the device sampler's weights and block sums per member (GPU only).
 * ``train_population`` -- ``hockey_amd.td3.train`` for S members side by side: one VecHockeyEnv of S x n arenas, one
   ``hkl_act`` launch per step through a PolicyBank, one OpponentMix, one grouped learner.
 
@@ -64,8 +67,11 @@ class PopulationRing:
         self.d = torch.zeros(n, device=d)
         self.size_t = torch.zeros(self.S, dtype=torch.int64, device=d)
         self.pos_t = torch.zeros(self.S, dtype=torch.int64, device=d)
-        self._members = [_MemberRing(self, j) for j in range(self.S)]
+        self._members = [self._make_member(j) for j in range(self.S)]
         self._ar = torch.arange(self.S, device=d)
+
+    def _make_member(self, j):
+        return _MemberRing(self, j)
 
     def member(self, j):
         return self._members[j]
@@ -90,8 +96,106 @@ class PopulationRing:
         self.s2[dst] = s2
         self.d[dst] = d.float()
         counts = onehot.sum(0)
+        self._before_commit(counts, n)
         self.pos_t.copy_((self.pos_t + counts) % self.cap)
         self.size_t.copy_(torch.clamp(self.size_t + counts, max=self.cap))
+
+    def _before_commit(self, counts, n):
+        """Called by push with the per-member row counts ([S] int64 on the device) and the push's rows, while pos_t
+        and size_t still hold the values before the push."""
+
+
+class _MemberPrioritizedRing(_MemberRing):
+    """Member j of a PopulationPrioritizedRing with the attributes FusedLearner reads off a
+    hockey_amd.td3.DevicePrioritizedRing: ``per`` onto the member's slices, ``w``, ``beta``, ``last``."""
+
+    prioritized = True
+    device_sampler = True
+
+    def __init__(self, pop, j):
+        super().__init__(pop, j)
+        nb = pop.nblk
+        self.beta = pop.beta[j]
+        self.w = pop.w[j * pop.wstride:j * pop.wstride + pop.cap]
+        self._bsum, self._bpre, self._bmax = (t[j * nb:(j + 1) * nb] for t in (pop.bsum, pop.bpre, pop.bmax))
+        self._last, self._bown = pop.last[j * pop.cap:(j + 1) * pop.cap], pop.bown[j * nb:(j + 1) * nb]
+        self.last = torch.zeros(1, dtype=torch.long, device=pop.device)
+        self.per = pop.pers[j]
+
+
+class PopulationPrioritizedRing(PopulationRing):
+    """PopulationRing whose members carry prioritized replay's weights (hockey_amd.td3.DevicePrioritizedRing, S of
+    them): one storage per array of the sampler -- ``w`` [S * wstride], ``bsum`` / ``bpre`` / ``bmax`` [S * nblk],
+    ``last`` [S * capacity], ``bown`` [S * nblk] -- driven by the hkl_per_*_group kernels (include/hockey_learner.h).
+    wstride is the capacity rounded up to 4 floats, so that every member's weights start 16-byte aligned (the
+    kernels read a block as float4); the padding is never addressed.  GPU only.
+
+    ``prioritized``: one bool per member (default all true); a member with False is a plain uniform member
+    (``member(j).prioritized`` is False) whose weights are pushed but never read.  ``beta``: a scalar or one value
+    per member.  ``push`` is PopulationRing's ragged push plus ONE hkl_per_push_group over all S members: the write
+    positions, the per-member row counts and the fill levels after the push are taken on the device, nothing is read
+    back, and member j's weights and block sums are those of DevicePrioritizedRing.push of its rows.  Code that
+    stores to ``w`` itself calls ``refresh()`` afterwards."""
+
+    def __init__(self, S, capacity, prioritized=None, beta=0.15, init_weight=1e8, device="cuda:0", n_obs=18, n_act=4):
+        from . import _native, learner_hip as LH
+
+        if torch.device(device).type != "cuda":
+            raise _native.HockeyNativeError("the device prioritized replay sampler runs on the GPU only")
+        self._LH, self._L = LH, LH.lib()
+        S = int(S)
+        self.prioritized = [True] * S if prioritized is None else [bool(x) for x in prioritized]
+        self.beta = [float(x) for x in (beta if isinstance(beta, (list, tuple)) else [beta] * S)]
+        if len(self.prioritized) != S or len(self.beta) != S:
+            raise ValueError("prioritized and beta take one value per member")
+        if not 1 <= S <= GROUP_MAX:
+            raise ValueError(f"a population has 1 to {GROUP_MAX} members, got {S}")
+        cap = int(capacity)
+        d = torch.device(device)
+        nb = self.nblk = -(-cap // self._L.hkl_per_block())
+        self.wstride = -(-cap // 4) * 4
+        self.w = torch.full((S * self.wstride,), float(init_weight), device=d)
+        self.bsum = torch.zeros(S * nb, dtype=torch.float64, device=d)
+        self.bpre = torch.zeros(S * nb, dtype=torch.float64, device=d)
+        self.bmax = torch.zeros(S * nb, dtype=torch.float32, device=d)
+        self.last = torch.zeros(S * cap, dtype=torch.int32, device=d)
+        self.bown = torch.zeros(S * nb, dtype=torch.int32, device=d)
+        self.pers = None
+        super().__init__(S, cap, device=d, n_obs=n_obs, n_act=n_act)  # builds the members through _make_member
+        # the push's device arguments: fixed buffers, so that the launch reads what this push computed
+        self._push_args = torch.zeros((3, S), dtype=torch.int64, device=d)
+        self.refresh()
+
+    def _make_member(self, j):
+        if self.pers is None:
+            LH, nb, cap = self._LH, self.nblk, self.cap
+            at = lambda t, i: ctypes.c_void_p(t.data_ptr() + i * t.element_size())  # noqa: E731
+            self.pers = (LH.Per * self.S)(*[
+                LH.Per(cap, at(self.w, k * self.wstride), at(self.size_t, k), at(self.bsum, k * nb),
+                       at(self.bmax, k * nb), at(self.bpre, k * nb), at(self.last, k * cap), at(self.bown, k * nb))
+                for k in range(self.S)])
+            self._pers_dev = _upload(self.pers, self.device)
+        return _MemberPrioritizedRing(self, j) if self.prioritized[j] else _MemberRing(self, j)
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def refresh(self):
+        """Recompute every member's block sums and maxima from ``w`` and the fill levels."""
+        self._LH._check(self._L.hkl_per_refresh_group(self.pers, self._pers_dev.data_ptr(), self.S, self._stream()),
+                        "hkl_per_refresh_group")
+
+    def _before_commit(self, counts, n):
+        # hkl_per_push per member, before the fill levels change: the pushed blocks' sums are taken against the
+        # fill level after the push, which is passed (PopulationRing.push stores it next)
+        a = self._push_args
+        a[0].copy_(self.pos_t)
+        a[1].copy_(counts)
+        torch.clamp(self.size_t + counts, max=self.cap, out=a[2])
+        p = a.data_ptr()
+        self._LH._check(self._L.hkl_per_push_group(self.pers, self._pers_dev.data_ptr(), p, p + 8 * self.S,
+                                                   p + 16 * self.S, min(int(n), self.cap), self.S, self._stream()),
+                        "hkl_per_push_group")
 
 
 # ---------------------------------------------------------------------------------------------------- learner
@@ -104,7 +208,9 @@ class PopulationLearner:
     """Learner updates of S = len(agents) <= 64 TD3 agents, agent j on rings[j], at batch ``batch`` in the launches
     one agent takes (module docstring).  rng is "device" only: each member's slots and target noise come from its own
     Philox stream, keyed by its agent's seed.  Members may differ in seed, lr_q, lr_pol, wd_*, gamma, tau_* and the
-    target-noise scale / clip; batch_size, policy_update_freq (2) and the hidden width (256) must be equal.
+    target-noise scale / clip; batch_size, policy_update_freq (2) and the hidden width (256) must be equal.  A ring
+    may be a prioritized member of a PopulationPrioritizedRing (the device sampler; beta per member): uniform and
+    prioritized members mix freely, and any other prioritized ring raises.
 
     ``update(train_actor)`` is one grouped update, ``run(k)`` k of them with the (critic; critic + actor) pair
     captured as a HIP graph after ``warm_pairs`` eager pairs, as hockey_amd.td3.Learner.run does (a linear chain on
@@ -127,8 +233,9 @@ class PopulationLearner:
                 raise ValueError(f"member {j}: policy_update_freq must be 2, got {c.policy_update_freq}")
             if ag.actor.fc1.out_features != 256:
                 raise ValueError(f"member {j}: hidden width must be 256, got {ag.actor.fc1.out_features}")
-            if rings[j].prioritized:
-                raise ValueError(f"member {j}: prioritized replay has no grouped kernels")
+            if rings[j].prioritized and not getattr(rings[j], "device_sampler", False):
+                raise ValueError(f"member {j}: prioritized replay is grouped on the device sampler only (a member "
+                                 "of a PopulationPrioritizedRing), not on a ring with the whole-ring torch sampler")
         self.device = self.agents[0].device
         self.train_step = 0
         self.graph, self.warm_left = None, int(warm_pairs)
@@ -151,8 +258,20 @@ class PopulationLearner:
     def _gather(self):
         """The members' io structs as host arrays (kept: the grouped calls check them) and their device copies."""
         LH, S, ms = self.LH, self.S, self.members
-        h = {"sio": (LH.SampleIO * S)(*[f.sio for f in ms]), "cio": (LH.CriticIO * S)(*[f.cio for f in ms]),
+        h = {"cio": (LH.CriticIO * S)(*[f.cio for f in ms]),
              "aio": (LH.ActorIO * S)(*[f.aio for f in ms]), "adam_a": (LH.AdamIO * S)(*[f.adam["actor"] for f in ms])}
+        # the batch's slots: hkl_sample_group over the uniform members, hkl_per_sample_group over the prioritized
+        # ones, whose priorities hkl_per_update_group writes back; everything else runs over all S members
+        uni = [f for f in ms if f.psio is None]
+        per = [f for f in ms if f.psio is not None]
+        self.n_uniform, self.n_per = len(uni), len(per)
+        if uni:
+            h["sio"] = (LH.SampleIO * len(uni))(*[f.sio for f in uni])
+        if per:
+            h["psio"] = (LH.PerSampleIO * len(per))(*[f.psio for f in per])
+            h["puio"] = (LH.PerUpdateIO * len(per))(*[f.puio for f in per])
+            for f in per:
+                f.ring.last = f.idx  # as FusedLearner.update leaves it
         for k in ("c256", "c32", "a256", "a32"):
             n = len(ms[0].wg[k])
             h[k] = (LH.WgJob * (S * n))(*[f.wg[k][i] for f in ms for i in range(n)])
@@ -187,12 +306,17 @@ class PopulationLearner:
         L, S, B, h, ck = self.L, self.S, self.B, self.host, self.LH._check
         st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         d = self.dptr
-        ck(L.hkl_sample_group(h["sio"], d["sio"], S, st), "hkl_sample_group")
+        if self.n_uniform:
+            ck(L.hkl_sample_group(h["sio"], d["sio"], self.n_uniform, st), "hkl_sample_group")
+        if self.n_per:  # slots, target noise and importance weights
+            ck(L.hkl_per_sample_group(h["psio"], d["psio"], self.n_per, st), "hkl_per_sample_group")
         ck(L.hkl_critic_step_group(h["cio"], d["cio"], S, st), "hkl_critic_step_group")
         ck(L.hkl_wgrad_pair_group(h["c256"], d["c256"], 2, h["c32"], d["c32"], 2, B, S, st), "hkl_wgrad_pair_group")
         adam_c = "adam_c1" if train_actor else "adam_c0"
         ck(L.hkl_adam_group(h[adam_c], d[adam_c], S, st), "hkl_adam_group")
         ck(L.hkl_pack_group(h["pack_c"], d["pack_c"], 2, S, st), "hkl_pack_group")
+        if self.n_per:  # the TD errors become the sampled slots' priorities, where FusedLearner.update does it
+            ck(L.hkl_per_update_group(h["puio"], d["puio"], self.n_per, st), "hkl_per_update_group")
         if not train_actor:
             return
         ck(L.hkl_actor_step_group(h["aio"], d["aio"], S, st), "hkl_actor_step_group")
@@ -255,7 +379,7 @@ _SHARED = ("curriculum_name", "max_steps", "train_iters", "batch_size", "policy_
            "eval_interval")
 
 
-def _check_members(members):
+def _check_members(members, per_ok=False):
     from .opponents import CURRICULA
 
     out = []
@@ -267,8 +391,9 @@ def _check_members(members):
         raise ValueError(f"a population has 1 to {GROUP_MAX} members, got {len(out)}")
     c0 = out[0][0]
     for j, (c, _, _) in enumerate(out):
-        if c.prioritized_replay:
-            raise ValueError(f"member {j}: prioritized_replay is not supported by train_population")
+        if c.prioritized_replay and not per_ok:
+            raise ValueError(f"member {j}: prioritized_replay needs the device sampler's grouped kernels, so "
+                             "train_population supports it on a CUDA device only")
         if c.use_self_play and any(row[3] > 0 for row in CURRICULA[c.curriculum_name]):
             raise ValueError(f"member {j}: self-play (use_self_play with a self-play share in curriculum "
                              f"'{c.curriculum_name}') is not supported by train_population")
@@ -297,7 +422,11 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
       arena's scale, and it advances on every step in which one of its members is past the all-random phase.
     * Player 2 is one OpponentMix over all arenas (seeded by member 0), so the members share ``curriculum_name``,
       ``max_steps`` and ``train_iters`` (and batch_size, policy_update_freq, buffer_size, eval_interval).  Self-play
-      and prioritized replay are not supported: such a member raises ValueError.
+      is not supported: such a member raises ValueError.
+    * ``prioritized_replay`` is per member: on a CUDA device the ring is a PopulationPrioritizedRing with member j
+      prioritized as cfg_j says and beta_j = cfg_j.beta, every step's ragged push stores the new transitions'
+      priorities, and prioritized and uniform members share one population.  On a CPU device such a member raises
+      ValueError (the device sampler has no CPU form).
     * Resets (episode e of member j is seeded seed_j + e), ``episode_end`` ("max_steps" / "done"), the replay ratio
       and ``eval_fn(agent_j, episodes)`` follow ``train``, per member.
     * Updates start in the first round after which EVERY member's total_steps exceeds the batch -- a batched
@@ -314,13 +443,13 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
     from .opponents import OpponentMix
     from .policy_bank import PolicyBank
 
-    ms = _check_members(members)
+    dev = torch.device(device)
+    ms = _check_members(members, per_ok=dev.type == "cuda")
     if episode_end not in ("max_steps", "done"):
         raise ValueError("episode_end must be 'max_steps' or 'done'")
     S, n = len(ms), int(n_arenas)
     N = S * n
     c0 = ms[0][0]
-    dev = torch.device(device)
     planned = rounds * c0.max_steps * n
     agents = []
     for cfg, seed, resume in ms:
@@ -336,7 +465,11 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
                            seed=ms[0][1])
     mix = OpponentMix(N, c0.curriculum_name, False, c0.self_play_interval, c0.self_play_pool_size, dev, ms[0][1])
     cap = replay_capacity or max(c0.buffer_size, n * c0.max_steps)
-    ring = PopulationRing(S, cap, device=dev)
+    if any(c.prioritized_replay for c, _, _ in ms):
+        ring = PopulationPrioritizedRing(S, cap, prioritized=[c.prioritized_replay for c, _, _ in ms],
+                                         beta=[c.beta for c, _, _ in ms], device=dev)
+    else:
+        ring = PopulationRing(S, cap, device=dev)
     batch = int(c0.batch_size)
     learner = PopulationLearner(agents, [ring.member(j) for j in range(S)], batch, graphs=graphs)
     updates = updates_per_round if updates_per_round is not None else updates_for(c0, n, c0.max_steps, batch)

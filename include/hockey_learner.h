@@ -154,7 +154,8 @@ int hkl_sample(const hkl_sample_io *io, void *stream);
  *    at the same n_wide / n_narrow / batch.  hkl_pack_group packs net[0 .. n_nets) of every member.
  *  - hkl_adam_io.polyak is part of the struct: a caller that alternates it (the critic's Adam on critic-only and on
  *    critic + actor updates) keeps two device arrays.
- * Prioritized replay has no grouped form: the hkl_per_* calls below are single-member. */
+ * Prioritized replay has grouped forms of its own under the same contract: hkl_per_*_group, after the hkl_per_* calls
+ * below. */
 #define HKL_GROUP_MAX 64
 int hkl_sample_group(const hkl_sample_io *host, const hkl_sample_io *dev, int n_members, void *stream);
 int hkl_critic_step_group(const hkl_critic_io *host, const hkl_critic_io *dev, int n_members, void *stream);
@@ -220,6 +221,41 @@ int hkl_per_sample(const hkl_per_sample_io *io, void *stream);
 /* hkl_per_sample's importance weights alone, for the slots already in io->idx */
 int hkl_per_weights(const hkl_per_sample_io *io, void *stream);
 int hkl_per_update(const hkl_per_update_io *io, void *stream);
+
+/* ---- grouped prioritized replay: the hkl_per_* calls for n_members <= HKL_GROUP_MAX rings at once
+ * (hockey_amd/population.py PopulationPrioritizedRing), under the grouped forms' contract above: host is checked in
+ * full (every check of the single call, on every member) before anything is launched, dev holds the same bytes on the
+ * device, member m runs in grid slice blockIdx.y, and a failed check returns HKL_E_INVALID with the call, the member
+ * and the fault in hkl_last_error.  Every call is asynchronous on stream and graph-capturable, with no host
+ * synchronisation, no copy and no read-back, and its number of launches depends neither on n_members nor on any
+ * value held on the device.  Member m's results are bit for bit those of the single call on host[m], whatever the
+ * other members are: the kernels share the single kernels' bodies, and with them every fixed summation order (a
+ * block's slot-by-slot and lane-by-lane sums, the prefix scan, the importance weights' tree).
+ *
+ *  - In every call the members' cap must be equal (one block count, one grid), in the sample / weights / update calls
+ *    their batch too (any batch >= 1, as in the single calls), and every member's w must be 16-byte aligned (a block
+ *    is read as float4; a ring that is a slice of a larger storage is placed accordingly).
+ *  - The members' w, bsum, bmax, bpre, last and bown must be pairwise disjoint: that is the caller's contract.
+ *  - hkl_per_sample_group: prefix, draw and importance weights, three launches.  Per member u or counter must be
+ *    non-null; noise, iw, beta, seed, scale and clip are per member, noise and iw optional per member (a member
+ *    without iw takes no weights).  hkl_per_weights_group: the importance weights alone for the slots already in idx
+ *    (iw required), one launch.  hkl_per_update_group: mark, write and touch, three launches.
+ *  - hkl_per_refresh_group recomputes every block of every member against its *size: one launch.
+ *  - hkl_per_push_group: pos, n and size_after are DEVICE arrays int64[n_members].  A member with n[m] > 0 gets
+ *    exactly hkl_per_push(&host[m], pos[m], n[m], size_after[m]): the maximum of w[0 : size_after) before the call is
+ *    stored to the n pushed slots, wrapping, and the covered blocks are recomputed against size_after (the caller
+ *    stores it to *size, before or after the call).  A member with n[m] == 0 is untouched.  max_n is the host's upper
+ *    bound on every n[m], 1 <= max_n <= cap: it sizes the grid, which covers the blocks a push of max_n slots can
+ *    touch (head and wrapped tail); waves with nothing to do exit.  Two launches.  0 <= n[m] <= max_n, 0 <= pos[m] <
+ *    cap and n[m] <= size_after[m] <= cap are the caller's contract, which the host cannot check; the kernels cut a
+ *    count to max_n and a fill level to cap and skip a member whose pos lies outside the ring, so values outside the
+ *    contract never address memory outside the member's arrays. */
+int hkl_per_sample_group(const hkl_per_sample_io *host, const hkl_per_sample_io *dev, int n_members, void *stream);
+int hkl_per_weights_group(const hkl_per_sample_io *host, const hkl_per_sample_io *dev, int n_members, void *stream);
+int hkl_per_update_group(const hkl_per_update_io *host, const hkl_per_update_io *dev, int n_members, void *stream);
+int hkl_per_refresh_group(const hkl_per *host, const hkl_per *dev, int n_members, void *stream);
+int hkl_per_push_group(const hkl_per *host, const hkl_per *dev, const int64_t *pos, const int64_t *n,
+                       const int64_t *size_after, int64_t max_n, int n_members, void *stream);
 
 /* y = the kernels' tanh of x (n floats; a test probe of the activation's accuracy) */
 int hkl_tanh_probe(const float *x, float *y, int64_t n, void *stream);

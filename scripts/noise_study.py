@@ -22,7 +22,8 @@ At the end the best checkpoint is re-evaluated on ``--final-games`` fresh placem
 Writes <out>/<protocol>_<noise>_s<seed>.json after every evaluation and the best actor's weights (reference td3
 ``policy`` layout) as <...>_best_actor.pt whenever it changes.
 
-``--population`` runs all four noises x ``--seeds`` as the members of ONE process (hockey_amd.population: grouped
+``--population`` runs all four noises x ``--seeds`` (``--protocol sp_per --sp 0``: prioritized replay off and on x
+``--seeds``, on the grouped prioritized-replay kernels) as the members of ONE process (hockey_amd.population: grouped
 learner kernels, one env of members x arenas arenas) and writes the same per-run files; the members' collection
 randomness is then shared (train_population docstring), each member's learner stream stays its own.
 
@@ -124,16 +125,20 @@ def main():
     n = args.arenas
     rounds = args.episodes // n
     if args.population:
-        if args.protocol == "sp_per":
-            ap.error("--population: the sp_per protocol switches prioritized replay and self-play, which "
-                     "train_population does not support")
+        if args.protocol == "sp_per" and args.sp:
+            ap.error("--population: --sp 1 switches self-play on, which train_population does not support")
         from hockey_amd.population import train_population
 
-        runs = [Run(args, noise, int(seed)) for noise in sorted(NOISES) for seed in args.seeds.split(",")]
-        by_member = {(r.cfg.noise_mode, r.seed): r for r in runs}
+        seeds = [int(seed) for seed in args.seeds.split(",")]
+        if args.protocol == "sp_per":  # the PER-off and PER-on cells of the self-play-off row, side by side
+            runs = [Run(args, "ou", seed, per=per) for per in (0, 1) for seed in seeds]
+        else:
+            runs = [Run(args, noise, seed) for noise in sorted(NOISES) for seed in seeds]
+        key = lambda cfg, seed: (cfg.noise_mode, bool(cfg.prioritized_replay), seed)  # noqa: E731
+        by_member = {key(r.cfg, r.seed): r for r in runs}
         members = [(r.cfg, r.seed, r.resume) if r.resume else (r.cfg, r.seed) for r in runs]
         _, stats = train_population(members, n_arenas=n, rounds=rounds, device="cuda:0", episode_end="done",
-                                    eval_fn=lambda ag, ep: by_member[(ag.cfg.noise_mode, ag.seed)].eval_fn(ag, ep))
+                                    eval_fn=lambda ag, ep: by_member[key(ag.cfg, ag.seed)].eval_fn(ag, ep))
         torch.cuda.synchronize()
         for r, st in zip(runs, stats):
             r.out["population"] = len(runs)  # collection randomness is shared by the population's members
@@ -153,14 +158,15 @@ class Run:
     """One (protocol, noise, seed) run's record: the JSON it writes after every evaluation, the best-checkpoint rule
     and the final re-evaluation.  The single-run path drives one; --population one per member."""
 
-    def __init__(self, args, noise, seed, dev="cuda:0"):
+    def __init__(self, args, noise, seed, dev="cuda:0", per=None):
         self.args, self.dev, self.seed = args, dev, seed
-        self.cfg, self.resume = config(args.protocol, noise, bool(args.per), bool(args.sp))
+        per = args.per if per is None else per  # --population --protocol sp_per runs both values
+        self.cfg, self.resume = config(args.protocol, noise, bool(per), bool(args.sp))
         cfg, resume, n = self.cfg, self.resume, args.arenas
         rounds = args.episodes // n
-        name = f"{args.protocol}_{noise}" if args.protocol != "sp_per" else f"sp_per_p{args.per}_sp{args.sp}"
+        name = f"{args.protocol}_{noise}" if args.protocol != "sp_per" else f"sp_per_p{int(per)}_sp{args.sp}"
         self.stem = os.path.join(args.out, f"{name}_s{seed}")
-        ref = (REFERENCE_SP_PER[(bool(args.per), bool(args.sp))] if args.protocol == "sp_per"
+        ref = (REFERENCE_SP_PER[(bool(per), bool(args.sp))] if args.protocol == "sp_per"
                else None if args.protocol == "stage1" else REFERENCE[noise])
         self.out = {"protocol": args.protocol, "noise": noise if args.protocol != "sp_per" else "ou", "seed": seed,
                     "per": bool(cfg.prioritized_replay), "self_play": bool(cfg.use_self_play), "config": vars(cfg),
