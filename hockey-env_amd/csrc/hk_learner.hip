@@ -332,13 +332,15 @@ __device__ __forceinline__ P4 philox(uint64_t key, P4 c) {
   }
   return c;
 }
-// sample e's replay slot of update `ctr` over `size` filled slots
-__device__ __forceinline__ int64_t sample_slot(uint64_t seed, int64_t e, uint64_t ctr, uint64_t size) {
+// sample e's replay slot of update `ctr` over `size` filled slots.  size <= 0 (an empty ring, or a fill word that is
+// out of contract) gives slot 0: out-of-contract device values are clamped, never addressed (as per_sample_body)
+__device__ __forceinline__ int64_t sample_slot(uint64_t seed, int64_t e, uint64_t ctr, int64_t size) {
+  if (size <= 0) return 0;
   const P4 r0 = philox(seed, P4{(uint32_t)e, (uint32_t)(e >> 32), (uint32_t)ctr, (uint32_t)(ctr >> 32)});
   const uint64_t bits = (((uint64_t)r0.x << 32) | r0.y) >> 11;
   const double u = (double)bits * (1.0 / 9007199254740992.0);
-  const uint64_t i = (uint64_t)(u * (double)size);
-  return (int64_t)(i < size ? i : size - 1);
+  const uint64_t i = (uint64_t)(u * (double)(uint64_t)size);
+  return (int64_t)(i < (uint64_t)size ? i : (uint64_t)size - 1);
 }
 // sample e's clipped target-smoothing noise of update `ctr`
 __device__ __forceinline__ f4 sample_noise(uint64_t seed, int64_t e, uint64_t ctr, float scale, float clip) {
@@ -366,8 +368,8 @@ __device__ __forceinline__ f4 sample_noise(uint64_t seed, int64_t e, uint64_t ct
 __device__ __forceinline__ void sample_body(const hkl_sample_io &io) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= io.batch) return;
-  const uint64_t ctr = (uint64_t)*io.counter, size = (uint64_t)*io.size;
-  io.idx[e] = sample_slot(io.seed, e, ctr, size);
+  const uint64_t ctr = (uint64_t)*io.counter;
+  io.idx[e] = sample_slot(io.seed, e, ctr, *io.size);
   *reinterpret_cast<f4 *>(io.noise + e * 4) = sample_noise(io.seed, e, ctr, io.scale, io.clip);
 }
 __global__ void __launch_bounds__(256) sample_kernel(hkl_sample_io io) { sample_body(io); }

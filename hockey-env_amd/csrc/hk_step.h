@@ -67,7 +67,21 @@ struct StepWords {
   double inc[2];
   float act[8];
   int32_t pol2;
+  int32_t bad_action;  // 1: an external value of this step was sanitised (HK_CNT_BAD_ACTION)
 };
+// The sanitising of external values (include/hockey.h, "Non-finite values"): a NaN action component and a
+// non-finite phase increment act as 0.  IEEE compares (no fast-math): only a NaN is unequal to itself, and only a
+// finite double compares <= DBL_MAX in magnitude.
+HK_DEV float action_or_zero(float x, int32_t &bad) {
+  const bool nan = x != x;
+  bad |= (int32_t)nan;
+  return nan ? 0.0f : x;
+}
+HK_DEV double increment_or_zero(double x, int32_t &bad) {
+  const bool fin = __builtin_fabs(x) <= 1.7976931348623157e308;
+  bad |= (int32_t)!fin;
+  return fin ? x : 0.0;
+}
 HK_DEV void fetch_words(StepWords &m, const DevState &s, const KCfg &cfg, const StepIO &io, int64_t a) {
 #pragma unroll
   for (int k = 0; k < NFF; ++k) m.f[k] = F(s, k, a);
@@ -79,10 +93,22 @@ HK_DEV void fetch_words(StepWords &m, const DevState &s, const KCfg &cfg, const 
   m.ph[1] = (cfg.policy[1] >= 2 || io.policy2) ? s.phase[s.n + a] : 0.0;
   m.ph[2] = io.policy2 ? s.phase[2 * s.n + a] : 0.0;
   m.pol2 = io.policy2 ? (int32_t)io.policy2[a] : 0;
+  // external values are sanitised here, under the wave-uniform branches that fetch them: a launch without
+  // io.actions / io.opp_inc (fused policies) executes none of it
+  m.bad_action = 0;
+  if (io.opp_inc) {
 #pragma unroll
-  for (int p = 0; p < 2; ++p) m.inc[p] = io.opp_inc ? io.opp_inc[a * 2 + p] : 0.0;
+    for (int p = 0; p < 2; ++p) m.inc[p] = increment_or_zero(io.opp_inc[a * 2 + p], m.bad_action);
+  } else {
+    m.inc[0] = m.inc[1] = 0.0;
+  }
+  if (io.actions) {
 #pragma unroll
-  for (int k = 0; k < 8; ++k) m.act[k] = io.actions ? io.actions[a * 8 + k] : 0.0f;
+    for (int k = 0; k < 8; ++k) m.act[k] = action_or_zero(io.actions[a * 8 + k], m.bad_action);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) m.act[k] = 0.0f;
+  }
 }
 
 // the register arena from its HBM words (f: NFF floats, iw: NIF ints)
@@ -352,7 +378,7 @@ HK_DEV void reset_lane(const DevState &s, const KCfg &cfg, int64_t a, const floa
 }
 
 // One HockeyEnv.step of arena a (policy actions, pre-solve laws, world.Step, outputs, then auto-reset).
-struct LaneOut { int done_edge, win1, win2, ntoi, ovf, nbig, bad_policy; };
+struct LaneOut { int done_edge, win1, win2, ntoi, ovf, nbig, bad_policy, bad_action; };
 
 // m: the step's HBM words (fetch_words), fetched by the caller so that it can issue them early
 HK_DEV void step_lane(const DevState &s, const KCfg &cfg, const StepIO &io, int64_t a, float *lds, int lane,
@@ -496,6 +522,7 @@ HK_DEV void step_lane(const DevState &s, const KCfg &cfg, const StepIO &io, int6
   out.ovf = w.overflow;
   out.nbig = w.n_big;
   out.bad_policy = bad_policy;
+  out.bad_action = m.bad_action;
 #ifdef HK_PHASE_TIMERS
   if (io.debug) {  // diagnostics build: per-lane work counters
     float *d = io.debug + a * 24;

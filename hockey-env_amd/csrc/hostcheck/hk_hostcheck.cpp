@@ -116,6 +116,7 @@ void hkh_step(void *h, const StepIO *io) {
     c->counters[5] += out.ovf;
     c->counters[6] += out.nbig;
     c->counters[7] += out.bad_policy;
+    c->counters[9] += out.bad_action;
   }
 }
 

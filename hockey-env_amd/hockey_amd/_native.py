@@ -21,6 +21,7 @@ STEP_SKIP_PHYSICS = 1
 DIAG_LARGE_ISLANDS = 1
 CNT_STEPS, CNT_EPISODES, CNT_GOALS_P1, CNT_GOALS_P2, CNT_TOI, CNT_OVERFLOW, CNT_LARGE_ISLANDS, CNT_BAD_POLICY = range(8)
 CNT_BAD_INDEX = 8  # snapshot / restore / copy entries with an index out of range (nothing copied); must stay 0
+CNT_BAD_ACTION = 9  # arena-steps with a NaN action component or a non-finite opp_inc (it acted as 0); must stay 0
 
 
 class HockeyNativeError(RuntimeError):

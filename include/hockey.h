@@ -69,10 +69,34 @@ enum {
   HK_CNT_LARGE_ISLANDS = 6, /* solver calls with more contacts than the register fast path holds */
   HK_CNT_BAD_POLICY = 7,    /* arena-steps whose io.policy2 entry was not an HK_POLICY_* id (that player
                                acted with zeros); must stay 0 */
-  HK_CNT_BAD_INDEX = 8      /* snapshot / restore / copy entries whose source or destination index was out of
+  HK_CNT_BAD_INDEX = 8,     /* snapshot / restore / copy entries whose source or destination index was out of
                                range (nothing was copied for them); must stay 0.  The phase-timer diagnostics build
-                               keeps its cycle sums in words 8..15 and shares this one */
+                               keeps its cycle sums in words 8..15 and shares this one and the next */
+  HK_CNT_BAD_ACTION = 9     /* arena-steps whose io.actions row held a NaN or whose io.opp_inc row held a non-finite
+                               value (each such value acted as 0, see "Non-finite values" below); must stay 0 */
 };
+
+/* Non-finite values.
+ *
+ * External per-step values are sanitised where the step fetches them (hk_step, hk_rollout, hk_step_host):
+ *   - a NaN component of io.actions acts as 0, whatever its sign bit or payload, for every one of the 8 components;
+ *   - a non-finite entry of io.opp_inc (NaN, +Inf, -Inf) acts as 0: the BasicOpponent's phase stands still;
+ *   - +-Inf and finite out-of-range actions keep clipping to +-1 as np.clip does (hockey_env.py:664); denormals and
+ *     -0.0 are ordinary values.
+ * Each arena-step that had at least one sanitised value adds one to HK_CNT_BAD_ACTION, whether or not the player it
+ * belongs to reads it in that step (a fused policy ignores its half of io.actions; the NaN in it still counts).
+ * The step is then bit for bit the step of the same row with 0 in place of each such value, io.actions_out
+ * included, and the state stays finite.  A launch without io.actions and io.opp_inc (fused policies) does no
+ * such work.
+ *
+ * Non-finite STATE is not sanitised.  It can enter through hk_set_state (a +-Inf position, angle or velocity, or
+ * velocities so large that a step overflows; a NaN there means "setter not called", see hk_set_state) or through
+ * hk_reset placement params.  For an arena that holds such a value:
+ *   - its state and every output row of it are unspecified, and so are its contributions to the counters;
+ *   - every step still terminates;
+ *   - no other arena changes: every arena reads and writes only its own rows;
+ *   - a masked hk_reset of that arena (finite params, or device placement) restores it fully: the next steps are
+ *     those of any freshly reset arena. */
 
 typedef struct hk_config {
   int32_t keep_mode;         /* HockeyEnv(keep_mode=True)  hockey_env.py:91 */

@@ -49,6 +49,8 @@ def lib():
                                          ctypes.c_double, _f64p, _f64p]
         L.hko_stats.argtypes = [ctypes.c_void_p, _i32p]
         L.hko_set_vel_ref.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        L.hko_bad_action.restype = ctypes.c_int
+        L.hko_bad_action.argtypes = [ctypes.c_void_p]
         L.hko_begin_contact.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
         u32p = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
         L.hko_philox.argtypes = [ctypes.c_uint64, u32p, u32p]
@@ -137,6 +139,10 @@ class OracleWorld:
         o = np.zeros(4, np.int32)
         self._L.hko_stats(self._w, o)
         return o
+
+    def bad_action(self):
+        """1 if the last step's action held a NaN (it acted as 0: the arena-step HK_CNT_BAD_ACTION counts)."""
+        return int(self._L.hko_bad_action(self._w))
 
 
 VAR_REVERSE, VAR_NO_BLOCK, VAR_NO_SLEEP, VAR_ITERS_8_3 = 1, 2, 4, 8
