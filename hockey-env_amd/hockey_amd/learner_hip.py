@@ -14,8 +14,8 @@ learner's own (Adam moments in fp32 device buffers): ``agent.opt_critic`` / ``op
 On a ``hockey_amd.td3.DevicePrioritizedRing`` the prioritized slots, importance weights and the priority write-back are
 the hkl_per_* kernels (per-block float64 sums; the slots come from the Philox stream under rng="device").
 
-``ActIO`` / ``hkl_act`` (actor inference over a bank of policies) is bound here and driven by
-``hockey_amd.policy_bank.PolicyBank``; ``ValueIO`` / ``hkl_value`` (twin-critic inference) by
+``ActIO`` / ``hkl_act`` (actor inference over a bank of policies) and ``ActWideIO`` / ``hkl_act_wide`` (the same over up
+to 4 096 policies) are bound here and driven by ``hockey_amd.policy_bank.PolicyBank``; ``ValueIO`` / ``hkl_value`` (twin-critic inference) by
 ``hockey_amd.value.ValueFn``.  The ``hkl_*_group`` forms (up to 64 independent learners per launch, each bit for bit
 its single call), ``hkl_per_*_group`` among them, are bound here and driven by
 ``hockey_amd.population.PopulationLearner`` and ``PopulationPrioritizedRing``.
@@ -37,6 +37,7 @@ MAX_SEG = 12
 CHUNK = 256  # batch granularity (include/hockey_learner.h)
 XP = 32
 ACT_MAX_POLICIES = 64  # HKL_ACT_MAX_POLICIES
+ACT_WIDE_MAX_POLICIES = 4096  # HKL_ACT_WIDE_MAX_POLICIES
 GROUP_MAX = 64  # HKL_GROUP_MAX: members of one grouped learner launch (hockey_amd.population)
 ACT_PARAM_FLOATS = 256 * 18 + 256 + 256 * 256 + 256 + 4 * 256 + 4  # HKL_ACT_PARAM_FLOATS: one bank slot's weights
 
@@ -113,6 +114,18 @@ class ActIO(ctypes.Structure):
                 ("out_col", ctypes.c_int32), ("order", vp), ("counts", vp), ("offsets", vp)]
 
 
+class ActWideIO(ctypes.Structure):
+    """hkl_act_wide_io: hkl_act over a bank of up to ACT_WIDE_MAX_POLICIES policies (hockey_amd.policy_bank)."""
+    _fields_ = [("n_policies", ctypes.c_int32), ("n_rows", ctypes.c_int32), ("params", vp), ("packs", vp),
+                ("obs", vp), ("obs_ld", ctypes.c_int64), ("policy", vp), ("out", vp), ("out_ld", ctypes.c_int64),
+                ("out_col", ctypes.c_int32), ("order", vp), ("counts", vp), ("offsets", vp), ("tiles", vp)]
+
+
+def act_wide_max_tiles(n_rows, n_policies):
+    """The bound on the non-empty 64-row tiles of hkl_act_wide: its ``tiles`` scratch holds 3 int32 per tile."""
+    return min(n_rows, -(-n_rows // 64) + n_policies)
+
+
 class ValueIO(ctypes.Structure):
     """hkl_value_io: twin-critic inference, Q(obs, act) or V(obs) = min Q(obs, actor(obs)) (hockey_amd.value)."""
     _fields_ = [("n_rows", ctypes.c_int32), ("actor", Net), ("q", Net * 2), ("obs", vp), ("obs_ld", ctypes.c_int64),
@@ -124,7 +137,8 @@ class ValueIO(ctypes.Structure):
 EXPORTS = ["hkl_last_error", "hkl_pack_floats", "hkl_pack", "hkl_critic_step", "hkl_actor_step", "hkl_wgrad",
            "hkl_wgrad_pair",
            "hkl_adam", "hkl_polyak", "hkl_tanh_probe", "hkl_sample", "hkl_per_block", "hkl_per_refresh",
-           "hkl_per_push", "hkl_per_sample", "hkl_per_weights", "hkl_per_update", "hkl_act", "hkl_act_io_size", "hkl_value",
+           "hkl_per_push", "hkl_per_sample", "hkl_per_weights", "hkl_per_update", "hkl_act", "hkl_act_io_size", "hkl_act_wide",
+           "hkl_act_wide_io_size", "hkl_value",
            "hkl_value_io_size", "hkl_sample_group", "hkl_critic_step_group", "hkl_actor_step_group",
            "hkl_wgrad_pair_group", "hkl_adam_group", "hkl_pack_group", "hkl_per_sample_group",
            "hkl_per_weights_group", "hkl_per_update_group", "hkl_per_refresh_group", "hkl_per_push_group"]
@@ -165,6 +179,7 @@ def lib():
         L.hkl_per_weights.argtypes = [ctypes.POINTER(PerSampleIO), vp]
         L.hkl_per_update.argtypes = [ctypes.POINTER(PerUpdateIO), vp]
         L.hkl_act.argtypes = [ctypes.POINTER(ActIO), vp]
+        L.hkl_act_wide.argtypes = [ctypes.POINTER(ActWideIO), vp]
         L.hkl_value.argtypes = [ctypes.POINTER(ValueIO), vp]
         # grouped forms: (host array, the same bytes on the device, ..., n_members, stream)
         L.hkl_sample_group.argtypes = [ctypes.POINTER(SampleIO), vp, ctypes.c_int, vp]
@@ -184,6 +199,8 @@ def lib():
             raise _native.HockeyNativeError("libhockey_learner.so pack size differs from hockey_amd.learner_hip")
         if L.hkl_act_io_size() != ctypes.sizeof(ActIO):
             raise _native.HockeyNativeError("libhockey_learner.so hkl_act_io differs from hockey_amd.learner_hip")
+        if L.hkl_act_wide_io_size() != ctypes.sizeof(ActWideIO):
+            raise _native.HockeyNativeError("libhockey_learner.so hkl_act_wide_io differs from hockey_amd.learner_hip")
         if L.hkl_value_io_size() != ctypes.sizeof(ValueIO):
             raise _native.HockeyNativeError("libhockey_learner.so hkl_value_io differs from hockey_amd.learner_hip")
         _lib = L

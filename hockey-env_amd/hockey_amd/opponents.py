@@ -32,6 +32,9 @@ snapshot on the device) writes the self-play arenas' actions into ``actions[:, 4
 pool member and no mask multiply.  Each done step is charged to the snapshot that arena faced at that step, as a
 per-step [pool][2] scatter-add on the device; ``end_round`` folds the steps in order (the snapshots' scores do
 not depend on each other, so the order across snapshots within a step is immaterial).
+
+``PopulationOpponentMix`` is the same for ``hockey_amd.population.train_population``: one pool per member, all of
+them in one wide PolicyBank, one ``select`` and one acting call per step for the whole population.
 """
 import copy
 import math
@@ -258,5 +261,192 @@ class OpponentMix:
                         self.pool.update_difficulty(idx, w, o)
             if actor is not None and episodes:
                 self.pool.step(actor, episodes)
+        self.reset_stats()
+        return out
+
+
+class PopulationOpponentMix:
+    """``OpponentMix`` for a population (``hockey_amd.population.train_population(self_play=...)``): member j owns
+    arenas [j n, (j + 1) n) and, if its config has ``use_self_play``, its own ``SelfPlayPool`` -- interval and size
+    from its config, seeded by its seed, scores and snapshots its own.  All pools mirror into ONE wide ``PolicyBank``
+    of S x (Pmax + 1) slots (Pmax: the largest pool size; member j's slots lie in [j (Pmax + 1), (j + 1) (Pmax + 1)))
+    and one ``PolicyBank.act`` call per step acts for every self-play arena of every member (``hkl_act_wide`` on the
+    GPU once the bank exceeds 64 slots).  The curriculum row is shared: the members share ``curriculum_name``
+    (``curriculum``: a name or a table, default the first member's).
+
+    The bot-or-self-play draws are ``OpponentMix._select_arena``'s, from one generator over the population (seeded
+    by the first member's seed); an arena can draw self-play only if its member uses it and that member's pool
+    holds a snapshot, otherwise it falls through to the bots.  sampling="arena": every arena draws its snapshot from
+    its own member's scores (one 2-D ``torch.multinomial`` over the [S, Pmax] score matrix; empty rows carry a dummy
+    weight and are masked out).  sampling="step": one snapshot per member and step.  Nothing is read back per step."""
+
+    update_schedule = OpponentMix.update_schedule
+
+    def __init__(self, members_cfg, seeds, n_arenas_per_member, device="cuda:0", sampling="arena", backend="auto",
+                 curriculum=None):
+        if sampling not in ("step", "arena"):
+            raise ValueError("sampling must be 'step' or 'arena'")
+        cfgs, seeds = list(members_cfg), [int(s) for s in seeds]
+        if not cfgs or len(cfgs) != len(seeds):
+            raise ValueError("one seed per member config")
+        self.S, self.n_per = len(cfgs), int(n_arenas_per_member)
+        self.n = self.S * self.n_per
+        self.device = dev = torch.device(device)
+        self.sampling, self.backend = sampling, backend
+        curriculum = cfgs[0].curriculum_name if curriculum is None else curriculum
+        self.table = CURRICULA[curriculum] if isinstance(curriculum, str) else [tuple(r) for r in curriculum]
+        self.pools = [SelfPlayPool(c.self_play_interval, c.self_play_pool_size, s) if c.use_self_play else None
+                      for c, s in zip(cfgs, seeds)]
+        self.pmax = max([p.pool_size for p in self.pools if p is not None] + [1])
+        self.stride = self.pmax + 1  # one slot more than a pool keeps: a snapshot is added before the oldest leaves
+        self.bank = None
+        if any(p is not None for p in self.pools):
+            from .policy_bank import PolicyBank
+
+            self.bank = PolicyBank(self.S * self.stride, dev, wide=True)
+        self.gen = torch.Generator(device=dev)
+        self.gen.manual_seed(seeds[0] + 0x5EED)
+        self.p_strong, self.p_weak, self.p_self = 0.0, 1.0, 0.0
+        self.update_schedule(0.0)
+        self.member_of = torch.arange(self.n, device=dev) // self.n_per  # [N] int64
+        self._policy2 = torch.empty(self.n, dtype=torch.uint8, device=dev)
+        self._minus1 = torch.full((), -1, dtype=torch.int32, device=dev)
+        self._pool_key = None
+        self.reset_stats()
+
+    # ------------------------------------------------------------------ pools
+    def pool_sizes(self):
+        return [len(p) if p is not None else 0 for p in self.pools]
+
+    def snapshot(self, members, actors):
+        """Append a snapshot of ``actors[i]`` to member ``members[i]``'s pool (score 1.0; the oldest is dropped past
+        the pool size and its slot freed for reuse); all bank slots are written by one ``replace_many``."""
+        slots, snaps = [], []
+        for j, actor in zip(members, actors):
+            pool = self.pools[j]
+            if pool is None:
+                raise ValueError(f"member {j} does not use self-play")
+            snap = copy.deepcopy(actor).eval()
+            for p in snap.parameters():
+                p.requires_grad_(False)
+            lo = j * self.stride
+            slot = next(k for k in range(lo, lo + pool.pool_size + 1) if k not in pool.slots)
+            pool.pool.append(snap)
+            pool.scores.append(1.0)
+            pool.slots.append(slot)
+            if len(pool.pool) > pool.pool_size:
+                pool.pool.pop(0)
+                pool.scores.pop(0)
+                self.bank.free(pool.slots.pop(0))
+            slots.append(slot)
+            snaps.append(snap)
+        if slots:
+            self.bank.replace_many(slots, snaps)
+
+    def _pool_tensors(self):
+        """([S, Pmax] scores with a dummy weight in empty rows, [S, Pmax] bank slots, [S] bool: the member can draw
+        self-play) on the device, rebuilt when a pool changed on the host."""
+        key = tuple((tuple(p.scores), tuple(p.slots)) if p is not None else None for p in self.pools)
+        if self._pool_key != key:
+            self._pool_key = key
+            scores = np.zeros((self.S, self.pmax), np.float32)
+            slots = np.full((self.S, self.pmax), -1, np.int32)
+            have = np.zeros(self.S, bool)
+            for j, p in enumerate(self.pools):
+                if p is not None and len(p):
+                    scores[j, :len(p)] = p.scores
+                    slots[j, :len(p)] = p.slots
+                    have[j] = True
+                else:
+                    scores[j, 0] = 1.0  # never used: the row's arenas cannot draw self-play
+            self._any = bool(have.any())
+            self._scores_t = torch.from_numpy(scores).to(self.device)
+            self._slots_t = torch.from_numpy(slots).to(self.device)
+            self._have_t = torch.from_numpy(have).to(self.device)
+        return self._scores_t, self._slots_t, self._have_t
+
+    # ------------------------------------------------------------------ per step
+    def reset_stats(self):
+        dev = self.device
+        self._counts = torch.zeros((self.S, 3), dtype=torch.int64, device=dev)  # per member: strong, weak, self-play
+        self._snap_counts = torch.zeros(self.S * self.pmax, dtype=torch.int64, device=dev)
+        self._outcomes = []  # per step: [S * Pmax][wins, others]
+        self._snap = None
+
+    def select(self, obs2, out=None):
+        """(policy2 [N] uint8, actions [N, 8] or None, bank slot per arena [N] int32 or None) for this step.  The
+        self-play arenas' player-2 actions are written into ``out[:, 4:8]`` (``out``: the caller's [N, 8] action
+        buffer, or one kept here); every other float of it is left alone."""
+        n, dev, S = self.n, self.device, self.S
+        scores, slots, have = self._pool_tensors()
+        u_sp = torch.rand(n, device=dev, generator=self.gen)
+        u_bot = torch.rand(n, device=dev, generator=self.gen)
+        sp = (u_sp < self.p_self) & have[self.member_of]
+        strong = ~sp & (u_bot < self.p_strong)
+        weak = ~sp & ~strong
+        p2 = self._policy2
+        p2.fill_(N.POLICY_BASIC_WEAK)
+        p2.masked_fill_(strong, N.POLICY_BASIC_STRONG)
+        p2.masked_fill_(sp, N.POLICY_EXTERNAL)
+        self._counts += torch.stack([strong.view(S, -1).sum(1), weak.view(S, -1).sum(1), sp.view(S, -1).sum(1)], 1)
+        self._sp_mask, self._snap = sp, None
+        if not self._any:
+            return p2, None, None
+        if self.sampling == "arena":  # pool index per arena, from the arena's own member's scores
+            snap = torch.multinomial(scores, self.n_per, replacement=True, generator=self.gen).reshape(n)
+        else:  # one per member and step
+            snap = torch.multinomial(scores, 1, generator=self.gen).expand(S, self.n_per).reshape(n)
+        policy = torch.where(sp, slots[self.member_of, snap], self._minus1)
+        if out is None:
+            if getattr(self, "_act8", None) is None:
+                self._act8 = torch.zeros((n, 8), dtype=torch.float32, device=dev)
+            out = self._act8
+        self.bank.act(obs2, policy, out=out, out_col=4, backend=self.backend)
+        self._snap = self.member_of * self.pmax + snap  # the (member, snapshot) each arena faces, flat
+        self._snap_counts.scatter_add_(0, self._snap, sp.to(torch.int64))
+        return p2, out, policy
+
+    def register_outcomes(self, done, reward):
+        """Done steps of this step's self-play arenas, charged to the (member, snapshot) the arena faced: agent win
+        (reward > 0) or not.  Tallied on the device; end_round() applies the steps in order."""
+        if self._snap is None:
+            return
+        d = (done != 0) & self._sp_mask
+        win = d & (reward > 0)
+        tally = torch.zeros((self.S * self.pmax, 2), dtype=torch.int64, device=self.device)
+        tally[:, 0].scatter_add_(0, self._snap, win.to(torch.int64))
+        tally[:, 1].scatter_add_(0, self._snap, (d & ~win).to(torch.int64))
+        self._outcomes.append(tally)
+
+    def end_round(self, actors=None, episodes=0):
+        """Per member: fold the round's outcomes, in step order, through its pool's ``update_difficulty``, advance its
+        pool by ``episodes`` (an int, or one per member) and snapshot ``actors[j]`` where an interval boundary was
+        crossed -- all crossing members in one ``replace_many``.  Returns one dict per member: its "strong" / "weak" /
+        "self_play" arena-steps and "snapshots", the arena-steps per snapshot of its pool (empty without a pool)."""
+        S, P = self.S, self.pmax
+        counts = self._counts.cpu().tolist()
+        faced = self._snap_counts.view(S, P).cpu().tolist()
+        out = []
+        for j, pool in enumerate(self.pools):
+            out.append({"strong": counts[j][0], "weak": counts[j][1], "self_play": counts[j][2],
+                        "snapshots": faced[j][:len(pool)] if pool is not None else []})
+        if self._outcomes:
+            steps = torch.stack(self._outcomes).cpu().numpy()  # [T][S * P][2]
+            for t, idx in zip(*np.nonzero(steps.any(-1))):  # row-major: the steps in order
+                j, i = divmod(int(idx), P)
+                pool = self.pools[j]
+                if pool is not None and i < len(pool):
+                    pool.update_difficulty(i, int(steps[t, idx, 0]), int(steps[t, idx, 1]))
+        if actors is not None:
+            eps = list(episodes) if isinstance(episodes, (list, tuple)) else [episodes] * S
+            crossed = []
+            for j, pool in enumerate(self.pools):
+                if pool is None or not eps[j]:
+                    continue
+                before = pool.episode_counter // pool.interval
+                pool.episode_counter += int(eps[j])
+                if pool.episode_counter // pool.interval > before:
+                    crossed.append(j)
+            self.snapshot(crossed, [actors[j] for j in crossed])
         self.reset_stats()
         return out

@@ -1,13 +1,14 @@
 """A bank of actors (18 -> 256 -> 256 -> 4, tanh; rl/td3/networks.py ActorNetwork) that act side by side.
 
-``PolicyBank(capacity, device)`` keeps up to ``capacity`` (at most 64) actors' weights in one strided device buffer
+``PolicyBank(capacity, device)`` keeps up to ``capacity`` (at most 64; with ``wide=True`` at most 4 096) actors' weights in one strided device buffer
 and runs, in ONE call, a different actor on every row of a batch: ``act(obs, policy)`` gives row i the actions of
 slot ``policy[i]`` and leaves rows with ``policy[i] = -1`` alone.  This is what per-arena self-play
 (``hockey_amd.opponents.OpponentMix(sampling="arena")``: every arena draws its own pool snapshot at every step, as
 the reference's single env does) and cross-play (``hockey_amd.evaluate.tournament``) need; with one masked PyTorch
 forward per slot either costs K forwards over the whole batch per step.
 
-backend="hip" is ``hkl_act`` (include/hockey_learner.h, csrc/hk_learner.hip): the rows are grouped by policy on the
+backend="hip" is ``hkl_act`` for capacities up to 64 and ``hkl_act_wide`` above (include/hockey_learner.h,
+csrc/hk_learner.hip; the two run one acting body, so a row's actions are the same bits): the rows are grouped by policy on the
 device and every workgroup runs 64 rows of one policy through the learner's fp32 MFMA layer routines; asynchronous
 on torch's current stream, graph-capturable, no host synchronisation.  A row's result does not depend on the other
 rows (bit for bit).  backend="torch" is the reference path: one masked eager forward per occupied slot, writing the
@@ -20,7 +21,8 @@ import ctypes
 import torch
 
 from . import _native
-from .learner_hip import ACT_MAX_POLICIES, ACT_PARAM_FLOATS, PACK_FLOATS, ActIO, Net
+from .learner_hip import (ACT_MAX_POLICIES, ACT_PARAM_FLOATS, ACT_WIDE_MAX_POLICIES, PACK_FLOATS, ActIO, ActWideIO, Net,
+                          act_wide_max_tiles)
 
 # floats of fc1.weight, fc1.bias, fc2.weight, fc2.bias, fc3.weight, fc3.bias inside a slot (torch layout, this order)
 _SHAPES = (("fc1.weight", (256, 18)), ("fc1.bias", (256,)), ("fc2.weight", (256, 256)), ("fc2.bias", (256,)),
@@ -51,15 +53,19 @@ def _hip_ready(device):
 class PolicyBank:
     """Up to ``capacity`` actors acting side by side (module docstring)."""
 
-    def __init__(self, capacity, device="cuda:0"):
+    def __init__(self, capacity, device="cuda:0", wide=False):
+        """wide: allow more than ``hkl_act``'s 64 slots, up to 4 096 (``hkl_act_wide`` under backend="hip").  Without it
+        the limit stays 64, as callers written against ``hkl_act`` expect."""
         self.capacity = int(capacity)
-        if not 1 <= self.capacity <= ACT_MAX_POLICIES:
-            raise ValueError(f"PolicyBank capacity must be in [1, {ACT_MAX_POLICIES}], got {capacity}")
+        limit = ACT_WIDE_MAX_POLICIES if wide else ACT_MAX_POLICIES
+        if not 1 <= self.capacity <= limit:
+            raise ValueError(f"PolicyBank capacity must be in [1, {limit}], got {capacity}"
+                             + ("" if wide else f" (wide=True allows up to {ACT_WIDE_MAX_POLICIES})"))
         self.device = torch.device(device)
         self.params = torch.zeros((self.capacity, ACT_PARAM_FLOATS), dtype=torch.float32, device=self.device)
         self.occupied = [False] * self.capacity
         self._packs = None  # [capacity][PACK_FLOATS], allocated with the first slot packed for the hip backend
-        self._scratch = {}  # n_rows -> (order, counts, offsets)
+        self._scratch = {}  # n_rows -> (order, counts, offsets), and tiles for a wide bank
 
     # ------------------------------------------------------------------ slots
     def __len__(self):
@@ -78,20 +84,37 @@ class PolicyBank:
     def replace(self, slot, actor):
         """Copy ``actor`` (a module with fc1 / fc2 / fc3, or its state dict) into ``slot`` and refresh the slot's
         MFMA operand pack; returns the slot."""
-        slot = self._slot(slot)
-        sd = actor.state_dict() if hasattr(actor, "state_dict") else dict(actor)
-        for name, (_, _, shape) in _OFF.items():
-            if name not in sd or tuple(sd[name].shape) != shape:
-                got = tuple(sd[name].shape) if name in sd else None
-                raise ValueError(f"PolicyBank holds actors 18 -> 256 -> 256 -> 4: {name} must be {shape}, got {got}")
-        row = self.params[slot]
+        return self.replace_many([slot], [actor])[0]
+
+    def replace_many(self, slots, actors):
+        """``replace`` for several slots at once: actor i goes to ``slots[i]`` and their operand packs are refreshed
+        together -- one ``hkl_pack`` call for up to the 4 networks it takes, one ``hkl_pack_group`` launch per 64
+        slots above that -- so a population-wide snapshot (at most 64 members) is one launch, not one per slot.
+        Returns the slots."""
+        slots = [self._slot(k) for k in slots]
+        actors = list(actors)
+        if len(slots) != len(actors):
+            raise ValueError("replace_many takes one actor per slot")
+        if len(set(slots)) != len(slots):
+            raise ValueError("replace_many: a slot is named twice")
+        sds = []
+        for actor in actors:
+            sd = actor.state_dict() if hasattr(actor, "state_dict") else dict(actor)
+            for name, (_, _, shape) in _OFF.items():
+                if name not in sd or tuple(sd[name].shape) != shape:
+                    got = tuple(sd[name].shape) if name in sd else None
+                    raise ValueError(f"PolicyBank holds actors 18 -> 256 -> 256 -> 4: {name} must be {shape}, "
+                                     f"got {got}")
+            sds.append(sd)
         with torch.no_grad():
-            for name, (o, n, _) in _OFF.items():
-                row[o:o + n].copy_(sd[name].detach().reshape(-1))
-        self.occupied[slot] = True
-        if _hip_ready(self.device):
-            self._pack(slot)
-        return slot
+            for slot, sd in zip(slots, sds):
+                row = self.params[slot]
+                for name, (o, n, _) in _OFF.items():
+                    row[o:o + n].copy_(sd[name].detach().reshape(-1))
+                self.occupied[slot] = True
+        if slots and _hip_ready(self.device):
+            self._pack(slots)
+        return slots
 
     def free(self, slot):
         self.occupied[self._slot(slot)] = False
@@ -111,15 +134,30 @@ class PolicyBank:
     def _stream(self):
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
-    def _pack(self, slot):
-        from .learner_hip import _check, lib
+    def _pack(self, slots):
+        """Refresh the operand packs of ``slots``: one ``hkl_pack`` for up to its 4 networks, else one
+        ``hkl_pack_group`` launch per 64 slots (one network per member of the group, no step counter)."""
+        from .learner_hip import GROUP_MAX, PackIO, _check, lib
 
         if self._packs is None:
             self._packs = torch.zeros((self.capacity, PACK_FLOATS), dtype=torch.float32, device=self.device)
-        base = self.params[slot].data_ptr()
-        p = [ctypes.c_void_p(base + 4 * _OFF[name][0]) for name, _ in _SHAPES]
-        net = (Net * 1)(Net(p[0], p[1], p[2], p[3], p[4], p[5], ctypes.c_void_p(self._packs[slot].data_ptr()), 18, 4))
-        _check(lib().hkl_pack(net, 1, None, self._stream()), "hkl_pack")
+        base, pbase = self.params.data_ptr(), self._packs.data_ptr()
+        nets = []
+        for slot in slots:
+            b = base + 4 * ACT_PARAM_FLOATS * slot
+            p = [ctypes.c_void_p(b + 4 * _OFF[name][0]) for name, _ in _SHAPES]
+            nets.append(Net(p[0], p[1], p[2], p[3], p[4], p[5], ctypes.c_void_p(pbase + 4 * PACK_FLOATS * slot), 18, 4))
+        if len(nets) <= 4:
+            _check(lib().hkl_pack((Net * len(nets))(*nets), len(nets), None, self._stream()), "hkl_pack")
+            return
+        for lo in range(0, len(nets), GROUP_MAX):
+            chunk = nets[lo:lo + GROUP_MAX]
+            ios = (PackIO * len(chunk))()
+            for io, net in zip(ios, chunk):
+                io.net[0] = net
+            dev = torch.frombuffer(bytearray(ios), dtype=torch.uint8).to(self.device)  # the same bytes on the device
+            _check(lib().hkl_pack_group(ios, ctypes.c_void_p(dev.data_ptr()), 1, len(chunk), self._stream()),
+                   "hkl_pack_group")
 
     def _act_hip(self, obs, policy, out, out_col, base_slot=0):
         from .learner_hip import _check, lib
@@ -130,7 +168,10 @@ class PolicyBank:
         if self._packs is None:
             raise _native.HockeyNativeError("PolicyBank backend='hip': no slot has been packed")
         n = obs.shape[0]
-        io = ActIO()
+        wide = policy is not None and self.capacity > ACT_MAX_POLICIES  # hkl_act's own range stays on hkl_act
+        if wide and n == 0:  # an empty tensor has no address to hand to the call, and there is nothing to write
+            return
+        io = ActWideIO() if wide else ActIO()
         io.n_rows = n
         io.params = self.params[base_slot].data_ptr()
         io.packs = self._packs[base_slot].data_ptr()
@@ -143,10 +184,21 @@ class PolicyBank:
             sc = self._scratch.get(n)
             if sc is None:
                 z = lambda m: torch.zeros(m, dtype=torch.int32, device=self.device)  # noqa: E731
-                sc = self._scratch[n] = (z(max(n, 1)), z(ACT_MAX_POLICIES + 1), z(ACT_MAX_POLICIES + 1))
+                if wide:
+                    K = self.capacity
+                    sc = (z(max(n, 1)), z(K + 1), z(K + 1), z(3 * max(act_wide_max_tiles(n, K), 1)))
+                else:
+                    sc = (z(max(n, 1)), z(ACT_MAX_POLICIES + 1), z(ACT_MAX_POLICIES + 1))
+                self._scratch[n] = sc
             io.policy = policy.data_ptr()
-            io.order, io.counts, io.offsets = (t.data_ptr() for t in sc)
-        _check(L.hkl_act(ctypes.byref(io), self._stream()), "hkl_act")
+            if wide:
+                io.order, io.counts, io.offsets, io.tiles = (t.data_ptr() for t in sc)
+            else:
+                io.order, io.counts, io.offsets = (t.data_ptr() for t in sc)
+        if wide:
+            _check(L.hkl_act_wide(ctypes.byref(io), self._stream()), "hkl_act_wide")
+        else:
+            _check(L.hkl_act(ctypes.byref(io), self._stream()), "hkl_act")
 
     # ------------------------------------------------------------------ torch (the reference path)
     def _forward_torch(self, slot, x):

@@ -14,7 +14,8 @@ the S members share every launch instead:
 * ``PopulationRing`` -- the S replay rings in one storage, filled by one ragged push per step;
   ``PopulationPrioritizedRing`` adds the device sampler's weights and block sums per member (GPU only).
 * ``train_population`` -- ``hockey_amd.td3.train`` for S members side by side: one VecHockeyEnv of S x n arenas, one
-  ``hkl_act`` launch per step through a PolicyBank, one OpponentMix, one grouped learner.
+  ``hkl_act`` launch per step through a PolicyBank, one OpponentMix, one grouped learner.  With ``self_play=`` the
+  members keep their own self-play pools in one ``PopulationOpponentMix`` over a wide PolicyBank (``hkl_act_wide``).
 
 What is and is not composition-independent: the LEARNER is -- its slots and target noise come from each member's own
 Philox stream (seeded by the agent's seed), its arithmetic from the member's own grid slice.  COLLECTION is not: the
@@ -379,7 +380,7 @@ _SHARED = ("curriculum_name", "max_steps", "train_iters", "batch_size", "policy_
            "eval_interval")
 
 
-def _check_members(members, per_ok=False):
+def _check_members(members, per_ok=False, self_play_ok=False):
     from .opponents import CURRICULA
 
     out = []
@@ -394,9 +395,10 @@ def _check_members(members, per_ok=False):
         if c.prioritized_replay and not per_ok:
             raise ValueError(f"member {j}: prioritized_replay needs the device sampler's grouped kernels, so "
                              "train_population supports it on a CUDA device only")
-        if c.use_self_play and any(row[3] > 0 for row in CURRICULA[c.curriculum_name]):
+        if c.use_self_play and not self_play_ok and any(row[3] > 0 for row in CURRICULA[c.curriculum_name]):
             raise ValueError(f"member {j}: self-play (use_self_play with a self-play share in curriculum "
-                             f"'{c.curriculum_name}') is not supported by train_population")
+                             f"'{c.curriculum_name}') is not supported by train_population without its self_play "
+                             "argument: pass self_play='arena' or 'step'")
         for k in _SHARED:
             if getattr(c, k) != getattr(c0, k):
                 raise ValueError(f"member {j}: {k} = {getattr(c, k)!r} differs from member 0's {getattr(c0, k)!r}; "
@@ -406,7 +408,7 @@ def _check_members(members, per_ok=False):
 
 def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode.NORMAL, episode_end="max_steps",
                      updates_per_round=None, eval_fn=None, on_step=None, env=None, replay_capacity=None, graphs=True,
-                     log=None, timing=False):
+                     log=None, timing=False, self_play=None):
     """``hockey_amd.td3.train`` for S = len(members) agents side by side in one process.  ``members`` is a list of
     (TD3Config, seed) or (TD3Config, seed, resume_from); member j owns arenas [j n, (j + 1) n) of one VecHockeyEnv of
     S * n_arenas arenas (``env``: a ready batch of that many arenas, e.g. the kernel source's host build in the CPU
@@ -421,8 +423,15 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
       ``noise_mode`` over that mode's arenas (unit scale, seeded by the mode's first member), multiplied by the
       arena's scale, and it advances on every step in which one of its members is past the all-random phase.
     * Player 2 is one OpponentMix over all arenas (seeded by member 0), so the members share ``curriculum_name``,
-      ``max_steps`` and ``train_iters`` (and batch_size, policy_update_freq, buffer_size, eval_interval).  Self-play
-      is not supported: such a member raises ValueError.
+      ``max_steps`` and ``train_iters`` (and batch_size, policy_update_freq, buffer_size, eval_interval).
+    * ``self_play``: None (the default) refuses a member with self-play (use_self_play and a self-play share in the
+      curriculum): ValueError.  "arena" or "step" accepts such members: player 2 is then one
+      ``hockey_amd.opponents.PopulationOpponentMix`` with a pool per self-play member -- the member's own interval,
+      pool size, scores and snapshots, seeded by its seed -- mirrored in one wide PolicyBank, and ONE ``act`` call per
+      step plays every self-play arena of the population ("arena": each arena draws its own snapshot per step;
+      "step": one snapshot per member and step).  Members with and without use_self_play may share a population.
+      ``stats[j]["opponents"]`` is then member j's own counts (with "snapshots") and ``stats[j]["pool_size"]`` its
+      pool's size after each round.  On a CPU device the mix runs on the bank's torch backend.
     * ``prioritized_replay`` is per member: on a CUDA device the ring is a PopulationPrioritizedRing with member j
       prioritized as cfg_j says and beta_j = cfg_j.beta, every step's ragged push stores the new transitions'
       priorities, and prioritized and uniform members share one population.  On a CPU device such a member raises
@@ -434,17 +443,21 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
     * on_step(member_of_row, arena_of_row, obs, action, reward, next_obs, done, step_result) sees every stored
       transition of a step, ragged over the members (test hook).
 
-    Collection randomness is shared: the exploration and opponent draws come from torch generators of the whole
-    population and the step kernel's device draws are keyed by the global arena id.  A member's trajectory therefore
+    Collection randomness is shared: the exploration and opponent draws (bot or self-play, which bot, and with
+    ``self_play`` which snapshot) come from torch generators of the whole population and the step kernel's device
+    draws are keyed by the global arena id.  The self-play pools, their scores and their snapshot schedule are per
+    member.  A member's trajectory therefore
     depends on its position in the population and on its size; only the learner is composition-independent (module
     docstring)."""
     import time
 
-    from .opponents import OpponentMix
+    from .opponents import OpponentMix, PopulationOpponentMix
     from .policy_bank import PolicyBank
 
     dev = torch.device(device)
-    ms = _check_members(members, per_ok=dev.type == "cuda")
+    if self_play not in (None, "arena", "step"):
+        raise ValueError("self_play must be None, 'arena' or 'step'")
+    ms = _check_members(members, per_ok=dev.type == "cuda", self_play_ok=self_play is not None)
     if episode_end not in ("max_steps", "done"):
         raise ValueError("episode_end must be 'max_steps' or 'done'")
     S, n = len(ms), int(n_arenas)
@@ -463,7 +476,10 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
 
         env = VecHockeyEnv(N, mode=mode, device=dev, policies=("external", "external"), auto_reset=False,
                            seed=ms[0][1])
-    mix = OpponentMix(N, c0.curriculum_name, False, c0.self_play_interval, c0.self_play_pool_size, dev, ms[0][1])
+    if self_play is None:
+        mix = OpponentMix(N, c0.curriculum_name, False, c0.self_play_interval, c0.self_play_pool_size, dev, ms[0][1])
+    else:
+        mix = PopulationOpponentMix([c for c, _, _ in ms], [s for _, s, _ in ms], n, dev, sampling=self_play)
     cap = replay_capacity or max(c0.buffer_size, n * c0.max_steps)
     if any(c.prioritized_replay for c, _, _ in ms):
         ring = PopulationPrioritizedRing(S, cap, prioritized=[c.prioritized_replay for c, _, _ in ms],
@@ -493,6 +509,9 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
               "replay_ratio": updates * batch / (n * c0.max_steps), "replay_capacity": cap, "critic_loss": [],
               "actor_loss": [], "mean_reward": [], "opponents": [], "evals": [], "round_time": [],
               "skipped_rounds": 0, "noise_scale": []} for _ in range(S)]
+    if self_play is not None:
+        for st in stats:
+            st["pool_size"] = []
     episodes, next_eval = 0, c0.eval_interval
     stop_at_done = episode_end == "done"
     sync = (lambda: torch.cuda.synchronize(dev)) if timing else (lambda: None)
@@ -535,10 +554,13 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
             if any(f < ag.cfg.start_steps for f, ag in zip(first, agents)):
                 rnd_rows = allr_t[member_of] | ((local + first_t[member_of]) < start_t[member_of])
                 a = torch.where(rnd_rows[:, None], torch.rand((N, 4), device=dev) * 2 - 1, a)
-            policy2, a2, _ = mix.select(obs2)
+            if self_play is None:
+                policy2, a2, _ = mix.select(obs2)
+                if a2 is not None:
+                    act8[:, 4:] = a2
+            else:  # the self-play arenas' actions go straight into act8[:, 4:8]
+                policy2, _, _ = mix.select(obs2, out=act8)
             act8[:, :4] = a
-            if a2 is not None:
-                act8[:, 4:] = a2
             res = env.step(act8, with_agent_two=True, policy2=policy2)
             o2, r, d = res.obs.clone(), res.reward.clone(), res.done.clone()
             for j in range(S):
@@ -562,12 +584,17 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
                 ep_reward += r
             obs, obs2 = o2, res.obs2.clone()
         episodes += n
-        opp = mix.end_round()
+        if self_play is None:
+            opp = [mix.end_round()] * S  # the population's counts: one mix over all arenas
+        else:
+            opp = mix.end_round([ag.actor for ag in agents], n)  # per member; snapshots precede the updates
         mean_r = ep_reward.view(S, n).mean(1).tolist()
         for j in range(S):
             stats[j]["env_steps"] += round_steps[j]
             stats[j]["mean_reward"].append(mean_r[j])
-            stats[j]["opponents"].append(opp)  # the population's counts: one mix over all arenas
+            stats[j]["opponents"].append(opp[j])
+            if self_play is not None:
+                stats[j]["pool_size"].append(mix.pool_sizes()[j])
             stats[j]["noise_scale"].append(agents[j].current_noise_scale)
         sync()
         t1 = time.perf_counter()

@@ -290,6 +290,35 @@ typedef struct {
 int hkl_act_io_size(void);
 int hkl_act(const hkl_act_io *io, void *stream);
 
+/* ---- actor inference over a wide bank (population self-play: one pool of snapshots per member) ----
+ * hkl_act's contract with K = n_policies in [1, HKL_ACT_WIDE_MAX_POLICIES]: params, packs, obs, policy and out as
+ * above, a row with policy[i] outside [0, K) is not written, no other float of out is, and a row's four actions are
+ * hkl_act's bit for bit (both acting kernels run one body).  policy == NULL: every row runs slot 0, no scratch.
+ * With policy given the caller provides the scratch (int32; contents on entry irrelevant, overwritten):
+ *   order   [n_rows]          the acting rows, grouped by policy
+ *   counts  [K + 1]           rows per policy (then the scatter's cursors); counts[K] = the number of tiles
+ *   offsets [K + 1]           exclusive scan of the counts
+ *   tiles   [3 * max_tiles]   (policy, first position in order, rows left in the group) of each 64-row tile,
+ *                             max_tiles = min(n_rows, (n_rows + 63) / 64 + K): a bound on the non-empty tiles
+ * Five launches whatever K and the device values are; the acting grid is max_tiles workgroups and the
+ * surplus ones leave at once.  Asynchronous on stream, graph-capturable, no host synchronisation, nothing read back.
+ * HKL_E_INVALID: K outside [1, 4096], n_rows < 0, obs_ld < 18, out_col < 0, out_ld < out_col + 4, a null params /
+ * packs / obs / out, or null scratch with policy given. */
+#define HKL_ACT_WIDE_MAX_POLICIES 4096
+typedef struct {
+  int32_t n_policies, n_rows;
+  const float *params, *packs;
+  const float *obs;
+  int64_t obs_ld;
+  const int32_t *policy;
+  float *out;
+  int64_t out_ld;
+  int32_t out_col;
+  int32_t *order, *counts, *offsets, *tiles;
+} hkl_act_wide_io;
+int hkl_act_wide_io_size(void);
+int hkl_act_wide(const hkl_act_wide_io *io, void *stream);
+
 /* ---- twin-critic inference (hockey_amd/value.py) ----
  * The clipped double-Q value of a TD3 agent outside the learner, one launch for n_rows rows:
  *   Q mode (act given):   q_k[i] = Q_k(obs[i * obs_ld .. + 18), unscale(act[i * act_ld .. + 4)))

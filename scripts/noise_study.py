@@ -22,8 +22,9 @@ At the end the best checkpoint is re-evaluated on ``--final-games`` fresh placem
 Writes <out>/<protocol>_<noise>_s<seed>.json after every evaluation and the best actor's weights (reference td3
 ``policy`` layout) as <...>_best_actor.pt whenever it changes.
 
-``--population`` runs all four noises x ``--seeds`` (``--protocol sp_per --sp 0``: prioritized replay off and on x
-``--seeds``, on the grouped prioritized-replay kernels) as the members of ONE process (hockey_amd.population: grouped
+``--population`` runs all four noises x ``--seeds`` (``--protocol sp_per``: the four prioritized-replay x self-play
+cells x ``--seeds``, or the cells ``--per`` / ``--sp`` leave open; self-play members keep their own pools and play
+them per arena, train_population(self_play="arena")) as the members of ONE process (hockey_amd.population: grouped
 learner kernels, one env of members x arenas arenas) and writes the same per-run files; the members' collection
 randomness is then shared (train_population docstring), each member's learner stream stays its own.
 
@@ -106,8 +107,10 @@ def deviations(protocol, episodes):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--protocol", choices=["scratch", "stage1", "stage2", "sp_per"], required=True)
-    ap.add_argument("--per", type=int, default=0, help="sp_per: prioritized replay on (1) / off (0)")
-    ap.add_argument("--sp", type=int, default=0, help="sp_per: self-play on (1) / off (0)")
+    ap.add_argument("--per", type=int, default=None, choices=[0, 1],
+                    help="sp_per: prioritized replay on (1) / off (0, the default; --population: both)")
+    ap.add_argument("--sp", type=int, default=None, choices=[0, 1],
+                    help="sp_per: self-play on (1) / off (0, the default; --population: both)")
     ap.add_argument("--noise", choices=sorted(NOISES), help="the run's noise (not with --population: it runs all)")
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--population", action="store_true",
@@ -125,25 +128,30 @@ def main():
     n = args.arenas
     rounds = args.episodes // n
     if args.population:
-        if args.protocol == "sp_per" and args.sp:
-            ap.error("--population: --sp 1 switches self-play on, which train_population does not support")
         from hockey_amd.population import train_population
 
         seeds = [int(seed) for seed in args.seeds.split(",")]
-        if args.protocol == "sp_per":  # the PER-off and PER-on cells of the self-play-off row, side by side
-            runs = [Run(args, "ou", seed, per=per) for per in (0, 1) for seed in seeds]
+        if args.protocol == "sp_per":  # the table's cells side by side: all four, or those --per / --sp leave open
+            pers = (0, 1) if args.per is None else (args.per,)
+            sps = (0, 1) if args.sp is None else (args.sp,)
+            runs = [Run(args, "ou", seed, per=per, sp=sp) for sp in sps for per in pers for seed in seeds]
         else:
             runs = [Run(args, noise, seed) for noise in sorted(NOISES) for seed in seeds]
-        key = lambda cfg, seed: (cfg.noise_mode, bool(cfg.prioritized_replay), seed)  # noqa: E731
+        key = lambda cfg, seed: (cfg.noise_mode, bool(cfg.prioritized_replay), bool(cfg.use_self_play),  # noqa: E731
+                                 seed)
         by_member = {key(r.cfg, r.seed): r for r in runs}
         members = [(r.cfg, r.seed, r.resume) if r.resume else (r.cfg, r.seed) for r in runs]
+        self_play = "arena" if any(r.cfg.use_self_play for r in runs) else None
         _, stats = train_population(members, n_arenas=n, rounds=rounds, device="cuda:0", episode_end="done",
-                                    eval_fn=lambda ag, ep: by_member[key(ag.cfg, ag.seed)].eval_fn(ag, ep))
+                                    eval_fn=lambda ag, ep: by_member[key(ag.cfg, ag.seed)].eval_fn(ag, ep),
+                                    self_play=self_play)
         torch.cuda.synchronize()
         for r, st in zip(runs, stats):
             r.out["population"] = len(runs)  # collection randomness is shared by the population's members
+            r.out["self_play_sampling"] = self_play
             r.finish(st)
         return
+    args.per, args.sp = int(args.per or 0), int(args.sp or 0)
     if args.noise is None:
         ap.error("--noise is required without --population")
     run = Run(args, args.noise, args.seed)
@@ -158,15 +166,16 @@ class Run:
     """One (protocol, noise, seed) run's record: the JSON it writes after every evaluation, the best-checkpoint rule
     and the final re-evaluation.  The single-run path drives one; --population one per member."""
 
-    def __init__(self, args, noise, seed, dev="cuda:0", per=None):
+    def __init__(self, args, noise, seed, dev="cuda:0", per=None, sp=None):
         self.args, self.dev, self.seed = args, dev, seed
-        per = args.per if per is None else per  # --population --protocol sp_per runs both values
-        self.cfg, self.resume = config(args.protocol, noise, bool(per), bool(args.sp))
+        per = int(args.per or 0) if per is None else per  # --population --protocol sp_per runs both values ...
+        sp = int(args.sp or 0) if sp is None else sp  # ... of both switches
+        self.cfg, self.resume = config(args.protocol, noise, bool(per), bool(sp))
         cfg, resume, n = self.cfg, self.resume, args.arenas
         rounds = args.episodes // n
-        name = f"{args.protocol}_{noise}" if args.protocol != "sp_per" else f"sp_per_p{int(per)}_sp{args.sp}"
+        name = f"{args.protocol}_{noise}" if args.protocol != "sp_per" else f"sp_per_p{int(per)}_sp{int(sp)}"
         self.stem = os.path.join(args.out, f"{name}_s{seed}")
-        ref = (REFERENCE_SP_PER[(bool(per), bool(args.sp))] if args.protocol == "sp_per"
+        ref = (REFERENCE_SP_PER[(bool(per), bool(sp))] if args.protocol == "sp_per"
                else None if args.protocol == "stage1" else REFERENCE[noise])
         self.out = {"protocol": args.protocol, "noise": noise if args.protocol != "sp_per" else "ou", "seed": seed,
                     "per": bool(cfg.prioritized_replay), "self_play": bool(cfg.use_self_play), "config": vars(cfg),
