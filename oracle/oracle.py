@@ -151,6 +151,8 @@ VAR_REST_THRESH0, VAR_ARITH_FRIC, VAR_NO_TOI, VAR_REST_MIN = 16, 32, 64, 128
 # goal-path variants (hk_oracle.c HKO_VAR_SENSOR_* / HKO_VAR_KEEP_COM)
 VAR_SENSOR_SKIN_PLUS, VAR_SENSOR_SKIN_MINUS, VAR_SENSOR_SWEPT, VAR_KEEP_COM = 256, 512, 1024, 2048
 VAR_SENSOR_CORE = 4096
+# deliberately wrong sleeping: negative controls of the sleep laws (tests/test_sleep_ref.py; hk_oracle.c HKO_VAR_*)
+VAR_WAKE_RESETS_TIMER, VAR_SLEEP_KEEPS_VELOCITY, VAR_SLEEP_PER_BODY, VAR_SLEEPER_DROPS_FORCE = 8192, 16384, 32768, 65536
 
 
 def set_variant(flags):
