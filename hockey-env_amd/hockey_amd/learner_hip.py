@@ -1,4 +1,5 @@
-"""ctypes binding of the fused fp32 MFMA TD3 learner (include/hockey_learner.h, csrc/hk_learner.hip).
+"""ctypes binding of the fused fp32 MFMA TD3 learner (include/hockey_learner.h; the C ABI in csrc/hk_learner.hip, its
+kernels in csrc/hkl_mlp.h, hkl_td3.h, hkl_per.h, hkl_act.h and hkl_value.h).
 
 ``FusedLearner(agent, ring, batch)`` performs ``agent``'s learner updates (rl/td3/learner.py:55-218: clipped
 double-Q target with policy smoothing, weighted smooth-L1 critic loss, delayed actor update, Polyak averaging, Adam
@@ -144,13 +145,6 @@ EXPORTS = ["hkl_last_error", "hkl_pack_floats", "hkl_pack", "hkl_critic_step", "
            "hkl_per_weights_group", "hkl_per_update_group", "hkl_per_refresh_group", "hkl_per_push_group"]
 
 
-def tanh_probe(x):
-    """The fused kernels' tanh of a device float32 tensor (accuracy check)."""
-    x = x.contiguous().float()
-    y = torch.empty_like(x)
-    _check(lib().hkl_tanh_probe(_p(x), _p(y), x.numel(),
-                                ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), "hkl_tanh_probe")
-    return y
 _lib = None
 
 
@@ -214,6 +208,15 @@ def _check(rc, what):
 
 def _p(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def tanh_probe(x):
+    """The fused kernels' tanh of a device float32 tensor (accuracy check)."""
+    x = x.contiguous().float()
+    y = torch.empty_like(x)
+    _check(lib().hkl_tanh_probe(_p(x), _p(y), x.numel(),
+                                ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), "hkl_tanh_probe")
+    return y
 
 
 def flatten_(module):

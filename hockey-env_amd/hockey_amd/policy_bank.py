@@ -8,7 +8,7 @@ the reference's single env does) and cross-play (``hockey_amd.evaluate.tournamen
 forward per slot either costs K forwards over the whole batch per step.
 
 backend="hip" is ``hkl_act`` for capacities up to 64 and ``hkl_act_wide`` above (include/hockey_learner.h,
-csrc/hk_learner.hip; the two run one acting body, so a row's actions are the same bits): the rows are grouped by policy on the
+csrc/hkl_act.h; the two run one acting body, so a row's actions are the same bits): the rows are grouped by policy on the
 device and every workgroup runs 64 rows of one policy through the learner's fp32 MFMA layer routines; asynchronous
 on torch's current stream, graph-capturable, no host synchronisation.  A row's result does not depend on the other
 rows (bit for bit).  backend="torch" is the reference path: one masked eager forward per occupied slot, writing the

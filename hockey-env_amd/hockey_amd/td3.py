@@ -271,7 +271,7 @@ class PrioritizedRing(ReplayRing):
 
 class DevicePrioritizedRing(PrioritizedRing):
     """PrioritizedRing whose push, sampling, importance weights and priority write-back run through the hkl_per_*
-    kernels (include/hockey_learner.h, csrc/hk_learner.hip) on float64 sums per block of ``hkl_per_block()`` slots,
+    kernels (include/hockey_learner.h, csrc/hkl_per.h) on float64 sums per block of ``hkl_per_block()`` slots,
     instead of passes over all ``cap`` slots: the same ``w`` tensor, the same distribution and write-back rule.
     ``sample_indices`` draws ``torch.rand(batch, dtype=float64)`` as PrioritizedRing does; the fused learner draws
     from its own Philox stream instead (FusedLearner, rng="device").  GPU only.  Code that stores to ``w`` itself

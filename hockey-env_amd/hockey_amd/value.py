@@ -10,7 +10,7 @@ into flat buffers of its own, as ``PolicyBank`` does, so a fused ``Learner`` att
 later training does not move the values until ``refresh()``.  The critic's ``action_low`` / ``action_range`` buffers
 give the action map.
 
-backend="hip" is ``hkl_value`` (include/hockey_learner.h, csrc/hk_learner.hip): one launch, 64 rows per workgroup
+backend="hip" is ``hkl_value`` (include/hockey_learner.h, csrc/hkl_value.h): one launch, 64 rows per workgroup
 through the learner's fp32 MFMA layer routines, the action of V mode kept in registers between the actor and the
 critics; asynchronous on torch's current stream, graph-capturable, no host synchronisation, a row's result independent
 of the other rows bit for bit.  backend="torch" is the reference path: the same expressions through

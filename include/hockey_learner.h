@@ -4,7 +4,9 @@
  * (:55-72): compute_target (:75-112), update_critic (:115-136), update_actor (:138-175) and soft_update (:196-218),
  * with Adam (rl/td3/agent.py:174-182).  hockey_amd/learner_hip.py binds it with ctypes; every pointer is a device
  * pointer (torch tensors' storage), every call is asynchronous on `stream` (a hipStream_t) and graph-capturable.
- * Batches are multiples of 256.  Returns HKL_OK or an error code; hkl_last_error() describes the last failure.
+ * Batches are multiples of 256.  Returns HKL_OK or an error code; hkl_last_error() describes the last failure: after
+ * every call that returns non-zero it reads "<entry point>: <what is wrong>".  A refused call (HKL_E_INVALID) has
+ * launched nothing.
  */
 #ifndef HOCKEY_LEARNER_H
 #define HOCKEY_LEARNER_H
@@ -18,7 +20,7 @@ extern "C" {
 #define HKL_E_INVALID 1
 #define HKL_E_DEVICE 2
 #define HKL_MAX_SEG 12
-/* floats of one network's MFMA operand pack (hk_learner.hip: f1, fp, bp, fo, wa) */
+/* floats of one network's MFMA operand pack (csrc/hkl_mlp.h: f1, fp, bp, fo, wa) */
 #define HKL_PACK_FLOATS (16 * 64 * 8 + 2 * 16 * 16 * 64 * 4 + 16 * 64 * 4 + 256 * 4)
 
 /* one MLP n_in -> 256 -> 256 -> n_out (tanh hidden; rl/td3/networks.py ActorNetwork): torch Linear weights
@@ -100,8 +102,11 @@ typedef struct {
 
 const char *hkl_last_error(void);
 int hkl_pack_floats(void);
-/* re-lay the weights of 1..4 networks out as MFMA operands; advances *step by one when step != NULL */
+/* re-lay the weights of 1..4 networks out as MFMA operands; advances *step by one when step != NULL.  Refused: a null
+ * nets, or a network with a null weight, bias or pack pointer (as hkl_pack_group refuses it). */
 int hkl_pack(const hkl_net *nets, int n_nets, int64_t *step, void *stream);
+/* Both refuse what their grouped forms refuse in a member: a batch that is no positive multiple of 256 and a null in
+ * any pointer the kernel dereferences unconditionally (every one but iw, td, sample_counter, p_db1 and p_db2). */
 int hkl_critic_step(const hkl_critic_io *io, void *stream);
 int hkl_actor_step(const hkl_actor_io *io, void *stream);
 /* weight-gradient job: slab[c][256][k_width] = sum over the samples j of chunk c (k_width 256: 512 samples each
@@ -112,12 +117,15 @@ typedef struct {
   const float *dz, *x;
   float *slab, *bias_slab;
 } hkl_wgrad_job;
-/* 1..4 jobs of one k_width (256 or 32) in one launch */
+/* 1..4 jobs of one k_width (256 or 32) in one launch.  A job with a null dz, x or slab is refused here and in
+ * hkl_wgrad_pair, as in hkl_wgrad_pair_group (bias_slab stays optional). */
 int hkl_wgrad(const hkl_wgrad_job *jobs, int n_jobs, int k_width, int64_t batch, void *stream);
 /* hkl_wgrad for n_wide k-width-256 jobs (dW2) and n_narrow k-width-32 jobs (dW1) in one launch (the same slabs as
  * the two hkl_wgrad calls, bit for bit). */
 int hkl_wgrad_pair(const hkl_wgrad_job *wide, int n_wide, const hkl_wgrad_job *narrow, int n_narrow, int64_t batch,
                    void *stream);
+/* Refused: n_seg outside [1, HKL_MAX_SEG], a null step, a segment with a null param / m / v / src (or target with
+ * polyak set), loss_src without loss_sum and loss_count -- the checks of hkl_adam_group on a member. */
 int hkl_adam(const hkl_adam_io *io, void *stream);
 /* target = target * rho + tau * param over n floats (soft_update; tau = 1 - rho) */
 int hkl_polyak(float *target, const float *param, int64_t n, float rho, float tau, void *stream);
@@ -132,6 +140,7 @@ typedef struct {
   float *noise;
   float scale, clip;
 } hkl_sample_io;
+/* Any batch >= 1 (hkl_sample_group: a multiple of 256); counter, size, idx and noise must not be null. */
 int hkl_sample(const hkl_sample_io *io, void *stream);
 
 /* ---- grouped forms: n_members <= HKL_GROUP_MAX independent learners in the launch one learner takes
@@ -166,7 +175,7 @@ int hkl_wgrad_pair_group(const hkl_wgrad_job *wide_host, const hkl_wgrad_job *wi
 int hkl_adam_group(const hkl_adam_io *host, const hkl_adam_io *dev, int n_members, void *stream);
 int hkl_pack_group(const hkl_pack_io *host, const hkl_pack_io *dev, int n_nets, int n_members, void *stream);
 
-/* ---- prioritized replay (rl/replay/prioritized_buffer.py) on per-block sums: csrc/hk_learner.hip ----
+/* ---- prioritized replay (rl/replay/prioritized_buffer.py) on per-block sums: csrc/hkl_per.h ----
  * Slot i of the ring has the sanitised weight p_i = max(nan_to_num(w_i, 0, 0, 0), 1e-6f) for i < *size and 0
  * otherwise; every sum of them is taken in float64 in a fixed order.  The ring's slots are cut into blocks of
  * HKL_PER_BLOCK; bsum / bmax hold each block's sum of p and its maximum raw weight (NaN propagates, as torch's max),

@@ -1,4 +1,4 @@
-// How much of critic_step's time is its seven 256x256 layer GEMMs (hk_learner.hip gemm256)?  The same grid and
+// How much of critic_step's time is its seven 256x256 layer GEMMs (hkl_mlp.h gemm256)?  The same grid and
 // workgroup shape as critic_step at batch 16 384 (256 workgroups x 4 waves, 16 samples per wave), the same
 // workgroup-collective gemm256 on a packed operand, 7 calls per wave (the critic step's count), timed with
 // events.  Build: hipcc --offload-arch=gfx950 -O3 -o learner_gemm_bench learner_gemm_bench.hip

@@ -38,7 +38,7 @@ from hockey_amd.td3 import TD3Config  # noqa: E402
 DEV = "cuda:0"
 TABLE = [(1.0, 0.35, 0.35, 0.3)]
 # floats one acting tile reads of its policy: the fc1 / fc2 / fc3 forward fragments of the operand pack
-# (csrc/hk_learner.hip kF1, kFp, kFo) and the three biases from the parameter block
+# (csrc/hkl_mlp.h kF1, kFp, kFo) and the three biases from the parameter block
 TILE_FLOATS = 16 * 64 * 8 + 16 * 16 * 64 * 4 + 16 * 64 * 4 + 256 + 256 + 4
 
 

@@ -163,7 +163,9 @@ def test_learner_ctypes_struct_layout_matches_header(tmp_path):
     from hockey_amd import learner_hip as LH
 
     probes = {"Net": "hkl_net", "CriticIO": "hkl_critic_io", "ActorIO": "hkl_actor_io", "Seg": "hkl_seg",
-              "AdamIO": "hkl_adam_io", "WgJob": "hkl_wgrad_job", "SampleIO": "hkl_sample_io"}
+              "AdamIO": "hkl_adam_io", "WgJob": "hkl_wgrad_job", "SampleIO": "hkl_sample_io", "Per": "hkl_per",
+              "PerSampleIO": "hkl_per_sample_io", "PerUpdateIO": "hkl_per_update_io", "PackIO": "hkl_pack_io",
+              "ActIO": "hkl_act_io", "ActWideIO": "hkl_act_wide_io", "ValueIO": "hkl_value_io"}
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "hockey_learner.h"', "int main(void) {"]
     for py, cname in probes.items():
         lines.append(f'  printf("{cname} %zu\\n", sizeof({cname}));')
@@ -202,6 +204,123 @@ def test_learner_adam_rejects_incomplete_io_before_any_launch():
     assert L.hkl_adam(ctypes.byref(io), None) == 1
     io.n_seg = 0
     assert L.hkl_adam(ctypes.byref(io), None) == 1
+
+
+def _pointers_set(s, addr=256):
+    """Every pointer field of a ctypes struct (nested structs and arrays included) set to a non-null fake address."""
+    for f, t in s._fields_:
+        if t is ctypes.c_void_p:
+            setattr(s, f, addr)
+        elif issubclass(t, ctypes.Structure):
+            _pointers_set(getattr(s, f), addr)
+        elif issubclass(t, ctypes.Array):
+            arr = getattr(s, f)
+            for i in range(len(arr)):
+                if t._type_ is ctypes.c_void_p:
+                    arr[i] = addr
+                elif issubclass(t._type_, ctypes.Structure):
+                    _pointers_set(arr[i], addr)
+    return s
+
+
+def test_learner_abi_refusals_name_the_entry_point():
+    """include/hockey_learner.h: "hkl_last_error() describes the last failure".  Every entry point of the learner
+    library that takes arguments refuses a malformed call with HKL_E_INVALID and a message that starts with its own
+    name, also right after ANOTHER entry point's refusal (a call that left the previous message in place would show
+    that one).  A single call refuses a struct with a null pointer that its kernel body dereferences, as the grouped
+    call on the same struct does.  No GPU needed: nothing here reaches a HIP call (the pointers are fakes)."""
+    from hockey_amd import learner_hip as LH
+
+    L = LH.lib()
+    byref, vp = ctypes.byref, ctypes.c_void_p
+    dev = vp(256)
+
+    def good(S, **kw):
+        s = _pointers_set(S())
+        for k, v in kw.items():
+            setattr(s, k, v)
+        return s
+
+    def good_adam(**kw):
+        io = good(LH.AdamIO, n_seg=1, **kw)
+        io.seg[0].rows = io.seg[0].cols = 8
+        return io
+
+    per = good(LH.Per, cap=2048)
+    jobs0, jobs1 = (LH.WgJob * 2)(), (LH.WgJob * 2)(good(LH.WgJob), good(LH.WgJob))
+    # name -> [(call, a word its message must hold or None)]: the first is a null io / array or the first range check,
+    # the rest are structs that are well-formed up to one null pointer
+    cases = {
+        "hkl_pack": [(lambda: L.hkl_pack(None, 1, None, None), "null"),
+                     (lambda: L.hkl_pack((LH.Net * 1)(good(LH.Net)), 0, None, None), "n_nets"),
+                     (lambda: L.hkl_pack((LH.Net * 1)(good(LH.Net, w2=None)), 1, None, None), "network")],
+        "hkl_critic_step": [(lambda: L.hkl_critic_step(None, None), "null"),
+                            (lambda: L.hkl_critic_step(byref(good(LH.CriticIO, batch=100)), None), "batch"),
+                            (lambda: L.hkl_critic_step(byref(good(LH.CriticIO, batch=256, ring_s=None)), None), "ring"),
+                            (lambda: L.hkl_critic_step(byref(good(LH.CriticIO, batch=256, p_loss=None)), None), "p_loss")],
+        "hkl_actor_step": [(lambda: L.hkl_actor_step(None, None), "null"),
+                           (lambda: L.hkl_actor_step(byref(good(LH.ActorIO, batch=256, idx=None)), None), "idx"),
+                           (lambda: L.hkl_actor_step(byref(good(LH.ActorIO, batch=256, dz2=None)), None), "dz2")],
+        "hkl_wgrad": [(lambda: L.hkl_wgrad(None, 1, 256, 256, None), "null"),
+                      (lambda: L.hkl_wgrad(jobs1, 2, 64, 256, None), "k_width"),
+                      (lambda: L.hkl_wgrad(jobs0, 2, 256, 256, None), "dz")],
+        "hkl_wgrad_pair": [(lambda: L.hkl_wgrad_pair(None, 1, None, 1, 256, None), "null"),
+                           (lambda: L.hkl_wgrad_pair(jobs1, 2, jobs0, 2, 256, None), "dz")],
+        "hkl_adam": [(lambda: L.hkl_adam(None, None), "null"),
+                     (lambda: L.hkl_adam(byref(good_adam(step=None)), None), "step")],
+        "hkl_polyak": [(lambda: L.hkl_polyak(dev, dev, 0, 0.5, 0.5, None), "n")],
+        "hkl_tanh_probe": [(lambda: L.hkl_tanh_probe(dev, dev, 0, None), "n")],
+        "hkl_sample": [(lambda: L.hkl_sample(None, None), "null"),
+                       (lambda: L.hkl_sample(byref(good(LH.SampleIO, batch=0)), None), "batch"),
+                       (lambda: L.hkl_sample(byref(good(LH.SampleIO, batch=5, size=None)), None), "size")],
+        "hkl_per_refresh": [(lambda: L.hkl_per_refresh(None, 0, 1, None), "null"),
+                            (lambda: L.hkl_per_refresh(byref(per), 2048, 1, None), "ring")],
+        "hkl_per_push": [(lambda: L.hkl_per_push(None, 0, 1, 1, None), "null"),
+                         (lambda: L.hkl_per_push(byref(per), 0, 8, 7, None), "size_after")],
+        "hkl_per_sample": [(lambda: L.hkl_per_sample(None, None), "null"),
+                           (lambda: L.hkl_per_sample(byref(good(LH.PerSampleIO, per=per, batch=0)), None), "batch")],
+        "hkl_per_weights": [(lambda: L.hkl_per_weights(None, None), "null"),
+                            (lambda: L.hkl_per_weights(byref(good(LH.PerSampleIO, per=per, batch=4, iw=None)), None), "iw")],
+        "hkl_per_update": [(lambda: L.hkl_per_update(None, None), "null"),
+                           (lambda: L.hkl_per_update(byref(good(LH.PerUpdateIO, per=per, batch=4, td=None)), None), "td")],
+        "hkl_act": [(lambda: L.hkl_act(None, None), "null"),
+                    (lambda: L.hkl_act(byref(good(LH.ActIO, n_policies=65, obs_ld=18, out_ld=4)), None), "n_policies"),
+                    (lambda: L.hkl_act(byref(good(LH.ActIO, n_policies=1, obs_ld=18, out_ld=4, counts=None)), None),
+                     "scratch")],
+        "hkl_act_wide": [(lambda: L.hkl_act_wide(None, None), "null"),
+                         (lambda: L.hkl_act_wide(byref(good(LH.ActWideIO, n_policies=65, obs_ld=18, out_ld=4, tiles=None)),
+                                                 None), "scratch"),
+                         (lambda: L.hkl_act_wide(byref(good(LH.ActWideIO, n_policies=4097, obs_ld=18, out_ld=4)), None),
+                          "n_policies")],
+        "hkl_value": [(lambda: L.hkl_value(None, None), "null")],
+        "hkl_sample_group": [(lambda: L.hkl_sample_group((LH.SampleIO * 1)(), dev, 0, None), "n_members")],
+        "hkl_critic_step_group": [(lambda: L.hkl_critic_step_group((LH.CriticIO * 1)(), dev, 0, None), "n_members")],
+        "hkl_actor_step_group": [(lambda: L.hkl_actor_step_group((LH.ActorIO * 1)(), dev, 0, None), "n_members")],
+        "hkl_wgrad_pair_group": [(lambda: L.hkl_wgrad_pair_group(jobs1, dev, 2, jobs1, dev, 2, 256, 0, None), "n_members"),
+                                 (lambda: L.hkl_wgrad_pair_group(jobs1, dev, 5, jobs1, dev, 2, 256, 1, None), "[1, 4]")],
+        "hkl_adam_group": [(lambda: L.hkl_adam_group((LH.AdamIO * 1)(), dev, 0, None), "n_members")],
+        "hkl_pack_group": [(lambda: L.hkl_pack_group((LH.PackIO * 1)(), dev, 1, 0, None), "n_members"),
+                           (lambda: L.hkl_pack_group((LH.PackIO * 1)(good(LH.PackIO)), dev, 5, 1, None), "n_nets")],
+        "hkl_per_sample_group": [(lambda: L.hkl_per_sample_group((LH.PerSampleIO * 1)(), dev, 0, None), "n_members")],
+        "hkl_per_weights_group": [(lambda: L.hkl_per_weights_group((LH.PerSampleIO * 1)(), dev, 0, None), "n_members")],
+        "hkl_per_update_group": [(lambda: L.hkl_per_update_group((LH.PerUpdateIO * 1)(), dev, 0, None), "n_members")],
+        "hkl_per_refresh_group": [(lambda: L.hkl_per_refresh_group((LH.Per * 1)(), dev, 0, None), "n_members")],
+        "hkl_per_push_group": [(lambda: L.hkl_per_push_group((LH.Per * 1)(), dev, dev, dev, dev, 1, 0, None), "n_members")],
+    }
+    no_arguments = {"hkl_last_error", "hkl_pack_floats", "hkl_per_block", "hkl_act_io_size", "hkl_act_wide_io_size",
+                    "hkl_value_io_size"}
+    names = [n for n in LH.EXPORTS if n not in no_arguments]
+    assert sorted(cases) == sorted(names), "every export that takes arguments needs a refused call here"
+
+    def err():
+        return L.hkl_last_error().decode()
+
+    for i, name in enumerate(names):
+        other = names[i - 1]
+        for call, word in cases[name]:
+            assert cases[other][0][0]() == 1 and err().startswith(other + ": "), (other, err())
+            assert call() == 1, name  # HKL_E_INVALID
+            assert err().startswith(name + ": ") and word in err()[len(name) + 2:], (name, word, err())
 
 
 def test_abi_rejects_invalid_arguments_before_any_launch():
