@@ -73,6 +73,7 @@ struct Arena {
   int n_toi, overflow, n_big;  // TOI events, island overflow flag, large-island (generic) solves
 #ifdef HK_PHASE_TIMERS
   int dg_vit_isl, dg_vit_toi, dg_pit, dg_toi_calls, dg_nc_max;  // diagnostics build: per-lane work
+  int dg_toi_lean;  // TOI events of this lane that took the lean one-contact path (toi_island_solve_one)
 #endif
   float *man;   // HBM manifolds
   float *ws;    // HBM slot workspace of large islands (HbmSlots)

@@ -279,8 +279,14 @@ HK_DEV float mask_f(float x, uint32_t m) { return __builtin_bit_cast(float, __bu
 
 // Diagnostic build only (make TIMERS=1): per-phase shader-clock accounting; compiled out otherwise.
 #ifdef HK_PHASE_TIMERS
+constexpr int kPhaseSlots = 18;
+// words per arena of StepIO::debug in this build: 0 wave cycles, 1-7 lane work, 8-20 phases 0-12, 21-23 velocity
+// families, 24-25 phases 16-17, 26 the lane's lean TOI events, 27 spare (scripts/tail_stats.py, scripts/tail_fit.py)
+constexpr int kTimerDebugWords = 28;
 struct PhaseT {
-  unsigned long long last, acc[16], fam[3];  // acc: phases 0-12 + the phase-0 split 13-15; fam: velocity-loop cycles in the general / two / one families
+  // acc: phases 0-12, the phase-0 split 13-15, the lean TOI event path's position passes 16 and velocity loop 17
+  // (the generic event path keeps 10 and 11); fam: velocity-loop cycles in the general / two / one families
+  unsigned long long last, acc[kPhaseSlots], fam[3];
 };
 #define HK_FAM_T0() const unsigned long long _ft0 = __builtin_amdgcn_s_memtime()
 #define HK_FAM_ADD(T, k) ((T).fam[k] += __builtin_amdgcn_s_memtime() - _ft0)

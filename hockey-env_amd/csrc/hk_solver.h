@@ -19,8 +19,13 @@ namespace hk {
 #ifdef HK_HOST_DIAG
 extern unsigned long long g_hk_host_diag[4];
 #define HK_HOST_DIAG_INC(k) (++g_hk_host_diag[k])
+// TOI events that took the lean one-contact path (hk_world.h toi_island_solve_one); a counter of its own, so the
+// four above keep their indices and hkh_diag its size
+extern unsigned long long g_hk_host_toi_lean;
+#define HK_HOST_TOI_LEAN_INC() (++g_hk_host_toi_lean)
 #else
 #define HK_HOST_DIAG_INC(k) ((void)0)
+#define HK_HOST_TOI_LEAN_INC() ((void)0)
 #endif
 
 
@@ -115,11 +120,18 @@ HK_DEV ManGeo man_geo(const Arena &w, int p) {
 }
 
 // b2ContactSolver constructor for one contact
-HK_DEV void fslot_load(FSlot &s, const Arena &w, int p, int warm, int isl) {
+HK_DEV void fslot_load(FSlot &s, const Arena &w, int p, int warm, int isl, const ManGeo *geo = nullptr) {
   const int pa = SLDS.pbodyA[p], pb = SLDS.pbodyB[p];
   const Quad *rec = man_rec(w, SLDS.manslot[p]);
-  const int meta = __float_as_int(rec[0].x);
-  const int count = meta & 0xff, type = meta >> 8;
+  int count, type;
+  if (geo) {  // the caller holds the record's geometry: no second read of it
+    count = geo->count;
+    type = geo->type;
+  } else {
+    const int meta = __float_as_int(rec[0].x);
+    count = meta & 0xff;
+    type = meta >> 8;
+  }
   s.bits = p | (isl << 5) | (pa << 7) | (pb << 11) | (count << 15) | (count << 17) | (type << 19);
   s.fr = SLDS.friction[p];
   s.mA = inv_mass(pa); s.mB = inv_mass(pb); s.iA = inv_inertia(pa); s.iB = inv_inertia(pb);
@@ -140,8 +152,9 @@ HK_DEV void fslot_load(FSlot &s, const Arena &w, int p, int warm, int isl) {
   s.sn[0] = s.sn[1] = s.sn[2] = s.sn[3] = 0u;
 }
 
-// InitializeVelocityConstraints for one contact
-HK_DEV void fslot_init_velocity(FSlot &s, const Arena &w) {
+// InitializeVelocityConstraints for one contact (geo: the contact's manifold geometry where the caller already
+// holds it, else it is read from the record here)
+HK_DEV void fslot_init_velocity(FSlot &s, const Arena &w, const ManGeo *geo = nullptr) {
   const Dyn &B = w.d;
   const float mA = s.mA, mB = s.mB, iA = s.iA, iB = s.iB;
   const int bA = fs_bA(s), bB = fs_bB(s), p = fs_pair(s);
@@ -163,7 +176,7 @@ HK_DEV void fslot_init_velocity(FSlot &s, const Arena &w) {
   xA.p = vsub(cA, mul_rv(xA.q, local_center(bA)));
   xB.p = vsub(cB, mul_rv(xB.q, local_center(bB)));
   // b2WorldManifold::Initialize
-  const ManGeo m = man_geo(w, p);
+  const ManGeo m = geo ? *geo : man_geo(w, p);
   v2 normal, pts[2];
   if (m.type == 1) {
     normal = mul_rv(xA.q, m.ln);

@@ -156,7 +156,7 @@ HK_DEV void unpack_arena(Arena &w, const float *fw, const int32_t *iw, int64_t a
   w.n_big = 0;
   w.force_big = 0;
 #ifdef HK_PHASE_TIMERS
-  w.dg_vit_isl = w.dg_vit_toi = w.dg_pit = w.dg_toi_calls = w.dg_nc_max = 0;
+  w.dg_vit_isl = w.dg_vit_toi = w.dg_pit = w.dg_toi_calls = w.dg_nc_max = w.dg_toi_lean = 0;
 #endif
   w.touch = (uint32_t)iw[I_TOUCH];
   w.enabled = (uint32_t)iw[I_ENABLED];
@@ -525,10 +525,11 @@ HK_DEV void step_lane(const DevState &s, const KCfg &cfg, const StepIO &io, int6
   out.bad_action = m.bad_action;
 #ifdef HK_PHASE_TIMERS
   if (io.debug) {  // diagnostics build: per-lane work counters
-    float *d = io.debug + a * 24;
+    float *d = io.debug + a * kTimerDebugWords;
     d[1] = (float)w.n_toi; d[2] = (float)w.dg_vit_isl; d[3] = (float)w.dg_vit_toi; d[4] = (float)w.dg_pit;
     d[5] = (float)w.dg_toi_calls; d[6] = (float)w.dg_nc_max; d[7] = (float)w.n_big;
     d[21] = (float)T.fam[0]; d[22] = (float)T.fam[1]; d[23] = (float)T.fam[2];
+    d[26] = (float)w.dg_toi_lean;  // 24, 25: the lean event path's phase cycles (hk_kernels.hip)
   }
 #endif
 }

@@ -168,6 +168,26 @@ HK_DEV void vone_family(FSlot &s, Dyn &B, int &it, bool &active, int first) {
   }
 }
 
+// The one-contact family for callers that know body A to be static on every lane (the lean TOI event path): the
+// kSA arms of vone_family alone, on body B's velocity in the caller's locals.  For such a lane vone_family picks
+// the same arms (its `sa` vote holds), reads body A as +0 and never writes it, and its snapshot words of body A are 0
+// either way: the same chunks, the same exit.  first == 7 as velocity_iterations starts its first family.
+HK_DEV int vone_family_static_a(FSlot &s, f2 &vB, float &wB) {
+  const int vc = fs_vcount(s);
+  f2 vA = f2{0.0f, 0.0f};
+  float wA = 0.0f;
+  uint32_t sn[10];
+#pragma unroll
+  for (int k = 0; k < 10; ++k) sn[k] = 0u;
+  Chunk c{0, 0, 7, true};
+  while (wave_any(c.active)) {
+    c.stop = chunk_end(c.it);
+    const bool p1 = !wave_any(c.active && vc != 1), p2 = !wave_any(c.active && vc != 2);
+    pick_points(p1, p2, [&](auto kP) { c = vone_chunk<true, decltype(kP)::value>(s, false, 0u, vA, wA, vB, wB, sn, c); });
+  }
+  return c.it;
+}
+
 // Two-contact family (at most two live contacts; a one-contact lane runs it with contact 1 masked off).
 // Each contact keeps its two bodies' velocities in locals; after a contact is solved, the other contact's
 // copy of any body it shares (equal body index) is refreshed from it, so every solve reads exactly the

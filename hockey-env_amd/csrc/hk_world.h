@@ -176,6 +176,127 @@ HK_DEV void toi_island_solve(Arena &w, SL &S, int minc, uint32_t extra, int nc, 
   sync_xf(w, db);
 }
 
+// The lean event path: a mini-island of ONE contact (99.7 % of TOI events, hk_body.h) between static body A and
+// dynamic body B = db, for the lanes of a round that hold one (the per-lane test in solve_toi).  It runs
+// toi_island_solve's float operations in toi_island_solve's order, for the values that path has in this case:
+//   * the manifold geometry is read once per event and serves the slot's meta word, every position pass and
+//     InitializeVelocityConstraints (the generic path reads the record 2 + passes times);
+//   * body A is static: its centre is the scene origin, its rotation (+0, 1), its inverse mass and inertia +0 (what
+//     inv_mass / inv_inertia / get_pos_a return for it), so nothing of A is gathered, tested or written; the
+//     arithmetic on A's centre is kept in a local as written (cA - 0 * P), so a non-finite impulse spreads as it does
+//     in fslot_solve_position;
+//   * body B's centre and angle stay in locals over the position passes and are written back once, with the leap
+//     of faith (c0 = c, a0 = a);
+//   * one constraint set-up, then the one-contact velocity family's static-body-A arms directly
+//     (vone_family_static_a): what velocity_iterations dispatches to for a wave of such lanes (first comparison at
+//     iteration 7, no slot swap), with the same vone_chunk arms, the 180-iteration cap, the period-4 exit and
+//     chunk_end, on body B's velocity in locals.
+template <int kType>
+HK_DEV float toi_one_position_pass(const ManGeo &m, int pcount, f2 &cA, f2 &cB, float &aB, f2 lcB, float mB, float iB,
+                                   float rBr) {
+  const float mA = 0.0f, iA = 0.0f, rAr = pair_rA();
+  const f2 lcA = f2{0.0f, 0.0f};
+  const f2 ln = F2(m.ln), lp = F2(m.lp);
+  float minSep = 0.0f;
+  HK_EV(EV_POS_PT, pcount);
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    if (j < pcount) {
+      rot qA, qB;
+      qA.s = 0.0f;  // rot_set(+0) == (+0, 1)
+      qA.c = 1.0f;
+      qB = rot_set(aB);
+      const f2 pA = cA - prv(qA, lcA), pB = cB - prv(qB, lcB);
+      f2 normal, point;
+      float sep;
+      if constexpr (kType == 1) {
+        normal = prv(qA, ln);
+        const f2 plane = prv(qA, lp) + pA;
+        const f2 clip = prv(qB, F2(m.pt[j])) + pB;
+        sep = pdot(clip - plane, normal) - rAr - rBr;
+        point = clip;
+      } else {
+        normal = prv(qB, ln);
+        const f2 plane = prv(qB, lp) + pB;
+        const f2 clip = prv(qA, F2(m.pt[j])) + pA;
+        sep = pdot(clip - plane, normal) - rAr - rBr;
+        point = clip;
+        normal = -normal;
+      }
+      const f2 rA = point - cA, rB = point - cB;
+      minSep = fmin2(minSep, sep);
+      float C = fclamp(kToiBaumgarte * (sep + kLinearSlop), -kMaxLinearCorrection, 0.0f);
+      float rnA = pcrs(rA, normal), rnB = pcrs(rB, normal);
+      float K = mA + mB + iA * rnA * rnA + iB * rnB * rnB;
+      float impulse = K > 0.0f ? -C / K : 0.0f;
+      const f2 P = bc(impulse) * normal;
+      cA = cA - bc(mA) * P;
+      cB = cB + bc(mB) * P;
+      aB += iB * pcrs(rB, P);
+    }
+  }
+  return minSep;
+}
+HK_DEV void toi_island_solve_one(Arena &w, int minc, int bA, int db, float sub_dt, PhaseT &T) {
+  HK_HOST_TOI_LEAN_INC();
+#ifdef HK_PHASE_TIMERS
+  w.dg_toi_lean++;
+#endif
+  HK_MARK(toi_lean_begin);
+  const ManGeo m = man_geo(w, minc);
+  FSlot s;
+  fslot_load(s, w, minc, 0, 0, &m);
+  {
+    const int pcount = fs_pcount(s);
+    const f2 lcB = F2(local_center(db));
+    const float mB = s.mB, iB = s.iB, rBr = pair_rB(db);
+    const f2 cA0 = f2{SLDS.spx[bA], SLDS.spy[bA]};
+    v2 c0;
+    float aB;
+    get_pos_b(w.d, db, c0, aB);
+    f2 cB = F2(c0);
+    // the manifold type is the event's: each type's passes are a loop of their own
+    const auto passes = [&](auto kType) {
+      for (int it = 0; it < 20; ++it) {
+        f2 cA = cA0;  // a static body's centre is not written back: every pass starts from the scene's
+        const float minSep = toi_one_position_pass<decltype(kType)::value>(m, pcount, cA, cB, aB, lcB, mB, iB, rBr);
+        if (minSep >= -1.5f * kLinearSlop) break;
+      }
+    };
+    if (m.type == 1) passes(kint<1>{});
+    else passes(kint<2>{});
+    HK_MARK(toi_lean_pos_end);
+    HK_TIC(T, 16);  // diagnostics: TOI position passes, lean path
+    // body B back to the body file together with the leap of faith (c0 = c, a0 = a)
+    place(w.d.cx, db, cB[0]);
+    place(w.d.cy, db, cB[1]);
+    place(w.d.a, db, aB);
+    place(w.d.c0x, db, cB[0]);
+    place(w.d.c0y, db, cB[1]);
+    place(w.d.a0, db, aB);
+  }
+  fslot_init_velocity(s, w, &m);
+  HK_MARK(toi_lean_vel_begin);
+  v2 vB2;
+  float wB;
+  get_vel_b(w.d, db, vB2, wB);
+  f2 vB = F2(vB2);
+  HK_FAM_T0();
+  const int it = vone_family_static_a(s, vB, wB);
+  HK_FAM_ADD(T, 2);
+  set_vel_b(w.d, db, V2(vB), wB);
+  HK_TIC(T, 17);  // diagnostics: TOI velocity iterations, lean path
+#ifdef HK_PHASE_TIMERS
+  w.dg_vit_toi += it;
+#endif
+  (void)it;
+#pragma unroll
+  for (int b = 0; b < 3; ++b)
+    if (b == db) integrate_one(sub_dt, w.d, b);
+  sync_xf(w, db);
+  HK_MARK(toi_lean_end);
+}
+
 // b2TimeOfImpact of static-vs-dynamic pair p from the two sweeps -> alpha in the step's [alpha0, 1] frame
 // (sB.alpha0 == max(alpha0 A, alpha0 B) after alignment)
 HK_DEV float toi_pair_sweeps(int p, const Sweep &sA, const Sweep &sB) {
@@ -471,7 +592,14 @@ HK_DEV void solve_toi(Arena &w, float dt, PhaseT &T) {
     HK_TIC(T, 9);  // diagnostics: TOI island build
     const float sub_dt = (1.0f - minAlpha) * dt;
     if (nc > kBigC) { w.overflow = 1; nc = kBigC; }
-    if (nc <= kToiC && !w.force_big) {
+    // Per lane: a one-contact mini-island on register slots takes the lean routine.  In a round whose event lanes
+    // all hold one (98.5 % of events on the bench workload) the wave runs the lean routine alone; in a mixed round
+    // the two groups run one after the other, each lane the routine its own contacts ask for.  A wave-uniform vote
+    // here (lean only if every event lane agrees) computed the same bits but made the kernel spill: 56 B of scratch
+    // per lane against 16 with this form (make resource-usage; DESIGN.md, Status at r19).
+    if (nc == 1 && !w.force_big) {
+      toi_island_solve_one(w, minc, bA, bB, sub_dt, T);
+    } else if (nc <= kToiC && !w.force_big) {
       RegSlots<kToiC> S;
       toi_island_solve(w, S, minc, extra, nc, bB, sub_dt, T);
     } else {

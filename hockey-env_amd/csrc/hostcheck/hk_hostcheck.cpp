@@ -42,6 +42,7 @@ constexpr hk::Scene g_scene =  // the kernels' compile-time scene (hk_scene_gen.
 #include "../hk_arena_copy.h"
 
 unsigned long long hk::g_hk_host_diag[4];
+unsigned long long hk::g_hk_host_toi_lean;
 unsigned long long hk::g_hk_flop_ev[hk::EV_N];
 
 using namespace hk;
@@ -161,6 +162,13 @@ int hkh_flop_event_count(void) { return hk::EV_N; }
 void hkh_diag(unsigned long long *out4) {
   std::memcpy(out4, hk::g_hk_host_diag, sizeof(hk::g_hk_host_diag));
   std::memset(hk::g_hk_host_diag, 0, sizeof(hk::g_hk_host_diag));
+}
+
+// TOI events that took the lean one-contact path (hk_world.h toi_island_solve_one), process-wide; read and cleared
+unsigned long long hkh_toi_lean(void) {
+  const unsigned long long n = hk::g_hk_host_toi_lean;
+  hk::g_hk_host_toi_lean = 0ull;
+  return n;
 }
 
 // ---- exact arena copies (hk_arena_copy.h): the kernel's copy_entry / copy_arena, one list entry after the other ----

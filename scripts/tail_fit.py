@@ -19,7 +19,11 @@ n = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 30
 env = VecHockeyEnv(n, device="cuda:0", policies=("strong", "strong"), auto_reset=True, seed=1)
 env.reset()
-dbg = torch.zeros((n, 24), dtype=torch.float32, device="cuda:0")
+WORDS = int(os.environ.get("HK_TIMER_WORDS", "28"))  # kTimerDebugWords (hk_core.h); 24 for a library older than the lean TOI path
+# the buffer always holds the widest layout a timers library writes, so a wrong HK_TIMER_WORDS can mis-read the
+# record but the kernel never writes past the buffer; the library's stride is the view's
+buf = torch.zeros(n * max(28, WORDS), dtype=torch.float32, device="cuda:0")
+dbg = buf[:n * WORDS].view(n, WORDS)
 io = N.StepIO()
 io.obs = env.obs_buf.data_ptr()
 io.reward = env.reward_buf.data_ptr()
@@ -32,9 +36,12 @@ for s in range(steps):
     env.step_raw(io)
     torch.cuda.synchronize()
     rows.append(dbg.cpu().numpy().copy())
-D = np.stack(rows).reshape(steps, n // 64, 64, 24)
+D = np.stack(rows).reshape(steps, n // 64, 64, WORDS)
 L = D[:, :, :, 1:8]  # ntoi, vit_isl, vit_toi, pit, toi_calls, nc_max, nbig
-P = D[:, :, 0, 8:21]  # lane-0 phase cycles
+P = D[:, :, 0, 8:21].copy()  # lane-0 phase cycles
+if WORDS >= 26:  # the lean event path's position passes and velocity loop, folded into the TOI event slots
+    P[:, :, 10] += D[:, :, 0, 24]
+    P[:, :, 11] += D[:, :, 0, 25]
 W = D[:, :, 0, 0]
 np.savez_compressed(os.path.join(ROOT, "gpurun_out", "tail_fit.npz"), lanes=L.astype(np.int16), phases=P,
                     wave=W)

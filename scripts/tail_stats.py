@@ -17,7 +17,12 @@ n = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 50
 env = VecHockeyEnv(n, device="cuda:0", policies=("strong", "strong"), auto_reset=True, seed=1)
 env.reset()
-dbg = torch.zeros((n, 24), dtype=torch.float32, device="cuda:0")
+WORDS = int(os.environ.get("HK_TIMER_WORDS", "28"))  # kTimerDebugWords (hk_core.h); 24 for a library older than the lean TOI path
+LEAN = WORDS >= 27  # words 24, 25: the lean event path's position / velocity cycles; 26: the lane's lean events
+# the buffer always holds the widest layout a timers library writes, so a wrong HK_TIMER_WORDS can mis-read the
+# record but the kernel never writes past the buffer; the library's stride is the view's
+buf = torch.zeros(n * max(28, WORDS), dtype=torch.float32, device="cuda:0")
+dbg = buf[:n * WORDS].view(n, WORDS)
 io = N.StepIO()
 io.obs = env.obs_buf.data_ptr()
 io.reward = env.reward_buf.data_ptr()
@@ -32,7 +37,12 @@ for s in range(steps):
     torch.cuda.synchronize()
     d = dbg.cpu().numpy().copy()
     rows.append(d)
-D = np.stack(rows)  # [steps, n, 24]: 0 wave cycles, 1-7 lane work, 8-19 wave phase cycles
+D = np.stack(rows)  # [steps, n, WORDS]: 0 wave cycles, 1-7 lane work, 8-20 wave phase cycles, 21-23 families, 24-26 lean
+if LEAN:  # the split by event path first (below), then the lean cycles join the TOI position / velocity slots so that
+    DL = D[:, :, 24:27].copy()  # every older figure of this script keeps its meaning
+    D[:, :, 18] += D[:, :, 24]
+    D[:, :, 19] += D[:, :, 25]
+D = D[:, :, :24]
 wave = D[:, ::64, 0]  # [steps, waves]
 print(f"wave cycles per step: mean {wave.mean():.0f}  median {np.median(wave):.0f}  p99 {np.percentile(wave, 99):.0f}  "
       f"max-per-step mean {wave.max(1).mean():.0f}")
@@ -97,6 +107,31 @@ if ev.any():
     print(f"lanes with >= 1 TOI event: {ev.mean() * 100:.2f}% of lane-steps; their own phase cycles (mean):")
     for k in (5, 6, 7, 8, 9, 10, 11):
         print(f"  {PH[k]:22s} {E[:, k].mean():10.0f}")
+# the event path by routine (r19): per event, the position and velocity cycles of the lean routine (a lane whose
+# mini-island has one contact on register slots: toi_island_solve_one) and of the generic one (toi_island_solve), each
+# from the lanes' own timers.  A lane's timer also counts the rounds it sits out exec-masked while other lanes run
+# theirs, so the per-event figures come from lanes with exactly one event in the step whose path is known.
+if LEAN:
+    ntoi, nlean = D[:, :, 1], DL[:, :, 2]
+    pos_l, vel_l = DL[:, :, 0], DL[:, :, 1]
+    pos_g, vel_g = D[:, :, 18] - pos_l, D[:, :, 19] - vel_l
+    tot_ev, tot_lean = ntoi.sum(), nlean.sum()
+    print(f"TOI events by path: lean {tot_lean:.0f} ({100 * tot_lean / max(tot_ev, 1):.2f}%)  generic {tot_ev - tot_lean:.0f}")
+    for nm, m, p, v in (("lean", (ntoi == 1) & (nlean == 1), pos_l, vel_l), ("generic", (ntoi == 1) & (nlean == 0), pos_g, vel_g)):
+        if m.any():
+            print(f"  {nm:8s} one-event lanes {m.sum():8d}: own-path cycles per event  position {p[m].mean():8.0f}  velocity {v[m].mean():8.0f}")
+    # per round: a wave has as many event rounds as its busiest lane has events; lane 0 waits the other lanes' events
+    # out in its "toi-min" slot, so that slot per round is what one round costs the wave -- by the routine its rounds
+    # took (all lean: every event of the wave was a lean one)
+    rounds = lanes[:, :, :, 1].max(2).reshape(-1)
+    tmin = D[:, ::64, 13].reshape(-1)
+    own = D[:, ::64, 1].reshape(-1)  # lane 0's own events run in its own slots, not in toi-min
+    all_lean = (DL[:, :, 2].reshape(steps, n // 64, 64).sum(2) == lanes[:, :, :, 1].sum(2)).reshape(-1)
+    for r in (1, 2, 3):
+        for nm, m in (("all lean", all_lean), ("some generic", ~all_lean)):
+            k = (rounds == r) & (own == 0) & m
+            if k.any():
+                print(f"  waves with {r} round(s), {nm:12s}: {k.sum():7d}  toi-min per round {tmin[k].mean() / r:8.0f}")
 # what bounds the launch (r05): the per-step maximum over waves, recomputed with each class of wave removed -- the most
 # a faster loop for that class could save (its waves would still cost something).  Classes: the contact count of the
 # wave's 180-iteration island lanes (0: none), a lane with >= 30 position passes, a lane with a 180-iteration TOI solve.
