@@ -201,21 +201,32 @@ def lib():
     return _lib
 
 
-def _check(rc, what):
+def check(rc, what):
     if rc != 0:
         raise _native.HockeyNativeError(f"{what} failed ({rc}): {lib().hkl_last_error().decode()}")
 
 
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
+ptr = _native.ptr  # raw device pointer of a tensor (None -> NULL)
+
+
+def stream_ptr(device):
+    """torch's current stream on ``device``, as the stream argument of every native call."""
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def upload(arr, device):
+    """The bytes of a ctypes array in device memory (uint8 tensor; the allocator's alignment exceeds any struct's)."""
+    return torch.frombuffer(bytearray(arr), dtype=torch.uint8).to(device)
+
+
+_check, _p = check, ptr  # the names older callers and the tests use
 
 
 def tanh_probe(x):
     """The fused kernels' tanh of a device float32 tensor (accuracy check)."""
     x = x.contiguous().float()
     y = torch.empty_like(x)
-    _check(lib().hkl_tanh_probe(_p(x), _p(y), x.numel(),
-                                ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), "hkl_tanh_probe")
+    _check(lib().hkl_tanh_probe(_p(x), _p(y), x.numel(), stream_ptr(x.device)), "hkl_tanh_probe")
     return y
 
 
@@ -318,7 +329,7 @@ class FusedLearner:
             self.puio = PerUpdateIO(ring.per, B, sio.idx, _p(self.buf["td"]))
         low = agent.critic.action_low.float().cpu().tolist()
         rng = agent.critic.action_range.float().cpu().tolist()
-        self._build_io(low, rng)
+        self._build_io(low, rng, G, C, C1, CA)
         # Adam adds each step's loss into a device accumulator: a private one until the caller sets its own, so
         # that an update never runs with the loss pointers unset
         self.set_loss_accumulator(torch.zeros(4, dtype=torch.float64, device=dev))
@@ -328,7 +339,7 @@ class FusedLearner:
         agent._fused_learner = self  # TD3.update / TD3.load now fail loudly (TD3._no_fused)
 
     # ------------------------------------------------------------------ structs (fixed pointers)
-    def _build_io(self, low, rng):
+    def _build_io(self, low, rng, G, C, C1, CA):
         b, n = self.buf, self.nets
         cio = CriticIO()
         cio.batch, cio.idx = self.B, _p(self.idx)
@@ -360,8 +371,6 @@ class FusedLearner:
         aio.p_db1, aio.p_db2, aio.p_dw3, aio.p_db3 = _p(b["pa_db1"]), _p(b["pa_db2"]), _p(b["pa_dw3"]), _p(b["pa_db3"])
         aio.p_loss = _p(b["loss_a"])
         self.aio = aio
-        G, C, C1 = self.B // 64, self.B // (512 if self.B % 512 == 0 else 256), self.B // 256
-        CA = self.B // 256
         # Adam segments: torch parameter order of each network (fc1.w, fc1.b, fc2.w, fc2.b, fc3.w, fc3.b)
         self.adam = {}
         for name, nets, lr, wd, tau in (
@@ -411,7 +420,7 @@ class FusedLearner:
                    "a32": (WgJob * 1)(J(b["dz1a"], b["x0a"], b["sa_w1"], b["sa_b1"]))}
 
     def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.agent.device).cuda_stream)
+        return stream_ptr(self.agent.device)
 
     def _pack(self, bufs, step, st):
         arr = (Net * len(bufs))(*[x.net for x in bufs])

@@ -71,24 +71,32 @@ class SelfPlayPool:
     def step(self, actor, episodes=1):
         """Count `episodes` finished training episodes; snapshot the actor when an interval boundary is crossed
         (at most one snapshot per call: a batched round crosses several boundaries with the same weights)."""
-        before = self.episode_counter // self.interval
-        self.episode_counter += int(episodes)
-        if self.episode_counter // self.interval > before:
+        if self.advance(episodes):
             self.add_snapshot(actor)
 
-    def add_snapshot(self, actor):
+    def advance(self, episodes):
+        """Count ``episodes`` finished training episodes; True when an interval boundary was crossed."""
+        before = self.episode_counter // self.interval
+        self.episode_counter += int(episodes)
+        return self.episode_counter // self.interval > before
+
+    def add_snapshot(self, actor, slot=None):
+        """Append a frozen copy of ``actor`` (score 1.0) and drop the oldest snapshot past ``pool_size``, freeing its
+        bank slot.  slot: the bank slot the caller chose and writes itself (default: the bank's first free slot,
+        written here).  Returns the copy."""
         snap = copy.deepcopy(actor).eval()
         for p in snap.parameters():
             p.requires_grad_(False)
         self.pool.append(snap)
         self.scores.append(1.0)
         if self.bank is not None:
-            self.slots.append(self.bank.add(snap))
+            self.slots.append(self.bank.add(snap) if slot is None else slot)
         if len(self.pool) > self.pool_size:
             self.pool.pop(0)
             self.scores.pop(0)
             if self.bank is not None:
                 self.bank.free(self.slots.pop(0))
+        return snap
 
     def update_difficulty(self, idx, wins, others):
         """One step's outcomes against snapshot ``idx``: ``others`` outcomes that are not agent wins (x1.2 each)
@@ -111,6 +119,55 @@ class SelfPlayPool:
 
     def __len__(self):
         return len(self.pool)
+
+
+def _draw(mix, can_sp):
+    """A step's bot-or-self-play draw for OpponentMix and PopulationOpponentMix: ``u_sp`` and then ``u_bot`` from
+    ``mix.gen``, self-play where u_sp < P(self-play) and ``can_sp`` allows it (a bool, or [N] bool on the device),
+    else the strong bot below P(strong) and the weak one above.  Fills ``mix._policy2``, adds the arena counts to
+    ``mix._counts`` ([rows, 3], the arenas split evenly over the rows) and returns the self-play mask."""
+    n, dev = mix.n, mix.device
+    u_sp = torch.rand(n, device=dev, generator=mix.gen)
+    u_bot = torch.rand(n, device=dev, generator=mix.gen)
+    if torch.is_tensor(can_sp):
+        sp = (u_sp < mix.p_self) & can_sp
+    else:
+        sp = (u_sp < mix.p_self) if can_sp else torch.zeros(n, dtype=torch.bool, device=dev)
+    strong = ~sp & (u_bot < mix.p_strong)
+    weak = ~sp & ~strong
+    p2 = mix._policy2
+    p2.fill_(N.POLICY_BASIC_WEAK)
+    p2.masked_fill_(strong, N.POLICY_BASIC_STRONG)
+    p2.masked_fill_(sp, N.POLICY_EXTERNAL)
+    mix._counts += torch.stack([strong, weak, sp]).view(3, mix._counts.shape[0], -1).sum(2).t()
+    mix._sp_mask = sp
+    return sp
+
+
+def _bank_act(mix, obs2, policy, out):
+    """One ``PolicyBank.act`` for the step's self-play arenas into ``out[:, 4:8]`` (``out``: the caller's [N, 8]
+    action buffer, or one kept by the mix); returns the buffer."""
+    if out is None:
+        if getattr(mix, "_act8", None) is None:
+            mix._act8 = torch.zeros((mix.n, 8), dtype=torch.float32, device=mix.device)
+        out = mix._act8
+    mix.bank.act(obs2, policy, out=out, out_col=4, backend=mix.backend)
+    return out
+
+
+def _outcomes(mix, done, reward):
+    """(agent wins, other outcomes) of this step's self-play arenas as [N] int64 masks."""
+    d = (done != 0) & mix._sp_mask
+    win = d & (reward > 0)
+    return win.to(torch.int64), (d & ~win).to(torch.int64)
+
+
+def _tally(mix, done, reward, size):
+    """A step's outcomes charged to the snapshot each arena faced (``mix._snap``): [size][wins, others] int64."""
+    tally = torch.zeros((size, 2), dtype=torch.int64, device=mix.device)
+    for col, hit in enumerate(_outcomes(mix, done, reward)):
+        tally[:, col].scatter_add_(0, mix._snap, hit)
+    return tally
 
 
 class OpponentMix:
@@ -149,7 +206,7 @@ class OpponentMix:
                 return
 
     def reset_stats(self):
-        self._counts = torch.zeros(3, dtype=torch.int64, device=self.device)  # strong, weak, self-play
+        self._counts = torch.zeros((1, 3), dtype=torch.int64, device=self.device)  # strong, weak, self-play
         self._outcomes = []  # per step: device tensor [snapshot index, wins, others] ("arena": [pool][wins, others])
         if self.bank is not None:  # arena-steps each snapshot (by pool index) was faced in this round
             self._snap_counts = torch.zeros(self.pool.pool_size, dtype=torch.int64, device=self.device)
@@ -168,29 +225,15 @@ class OpponentMix:
         """sampling="arena": (policy2 [N] uint8, actions [N,8] or None, bank slot per arena [N] int32 or None).
         The self-play arenas' player-2 actions are written into ``out[:, 4:8]`` (``out``: the caller's [N,8] action
         buffer, or one kept here); every other float of it is left alone."""
-        n, dev = self.n, self.device
-        have = len(self.pool) > 0
-        u_sp = torch.rand(n, device=dev, generator=self.gen)
-        u_bot = torch.rand(n, device=dev, generator=self.gen)
-        sp = (u_sp < self.p_self) if have else torch.zeros(n, dtype=torch.bool, device=dev)
-        strong = ~sp & (u_bot < self.p_strong)
-        weak = ~sp & ~strong
-        p2 = self._policy2
-        p2.fill_(N.POLICY_BASIC_WEAK)
-        p2.masked_fill_(strong, N.POLICY_BASIC_STRONG)
-        p2.masked_fill_(sp, N.POLICY_EXTERNAL)
-        self._counts += torch.stack([strong.sum(), weak.sum(), sp.sum()])
-        self._sp_mask, self._snap = sp, None
-        if not have:
+        dev = self.device
+        sp = _draw(self, len(self.pool) > 0)
+        p2, self._snap = self._policy2, None
+        if not len(self.pool):
             return p2, None, None
         scores, slots = self._pool_tensors()
-        snap = torch.multinomial(scores, n, replacement=True, generator=self.gen)  # pool index per arena
+        snap = torch.multinomial(scores, self.n, replacement=True, generator=self.gen)  # pool index per arena
         policy = torch.where(sp, slots[snap], torch.full((), -1, dtype=torch.int32, device=dev))
-        if out is None:
-            if getattr(self, "_act8", None) is None:
-                self._act8 = torch.zeros((n, 8), dtype=torch.float32, device=dev)
-            out = self._act8
-        self.bank.act(obs2, policy, out=out, out_col=4, backend=self.backend)
+        out = _bank_act(self, obs2, policy, out)
         self._snap = snap
         self._snap_counts.scatter_add_(0, snap, sp.to(torch.int64))
         return p2, out, policy
@@ -201,51 +244,32 @@ class OpponentMix:
         that mode only)."""
         if self.sampling == "arena" and self.pool is not None:
             return self._select_arena(obs2, out)
-        n, dev = self.n, self.device
-        idx = self.pool.sample() if self.pool is not None else None
-        u_sp = torch.rand(n, device=dev, generator=self.gen)
-        u_bot = torch.rand(n, device=dev, generator=self.gen)
-        sp = (u_sp < self.p_self) if idx is not None else torch.zeros(n, dtype=torch.bool, device=dev)
-        strong = ~sp & (u_bot < self.p_strong)
-        weak = ~sp & ~strong
-        p2 = self._policy2
-        p2.fill_(N.POLICY_BASIC_WEAK)
-        p2.masked_fill_(strong, N.POLICY_BASIC_STRONG)
-        p2.masked_fill_(sp, N.POLICY_EXTERNAL)
-        self._counts += torch.stack([strong.sum(), weak.sum(), sp.sum()])
+        idx = self.pool.sample() if self.pool is not None else None  # numpy's draw precedes the device draws
+        sp = _draw(self, idx is not None)
         act = None
         if idx is not None:
             with torch.no_grad():
                 act = self.pool.pool[idx](obs2)  # one batched PolicyOpponent forward for the step
             act = act * sp.unsqueeze(1)
-        self._sp_mask, self._idx = sp, idx
-        return p2, act, idx
+        self._idx = idx
+        return self._policy2, act, idx
 
     def register_outcomes(self, done, reward):
         """Done steps of this step's self-play arenas: agent win (reward > 0) or not (opponent_manager
         register_outcome -> update_difficulty).  Tallied per step on the device; end_round() applies the steps in
         order, clipping after every outcome."""
         if self.bank is not None:
-            if self._snap is None:
-                return
-            d = (done != 0) & self._sp_mask
-            win = d & (reward > 0)
-            tally = torch.zeros((self.pool.pool_size, 2), dtype=torch.int64, device=self.device)
-            tally[:, 0].scatter_add_(0, self._snap, win.to(torch.int64))
-            tally[:, 1].scatter_add_(0, self._snap, (d & ~win).to(torch.int64))
-            self._outcomes.append(tally)
-            return
-        if self._idx is None:
-            return
-        d = (done != 0) & self._sp_mask
-        win = d & (reward > 0)
-        self._outcomes.append(torch.stack([torch.full((), self._idx, dtype=torch.int64, device=self.device),
-                                           win.sum(), (d & ~win).sum()]))
+            if self._snap is not None:
+                self._outcomes.append(_tally(self, done, reward, self.pool.pool_size))
+        elif self._idx is not None:
+            win, other = _outcomes(self, done, reward)
+            self._outcomes.append(torch.stack([torch.full((), self._idx, dtype=torch.int64, device=self.device),
+                                               win.sum(), other.sum()]))
 
     def end_round(self, actor=None, episodes=0):
         """Fold the round's outcomes into the snapshot scores, advance the self-play episode counter (taking a
         snapshot on an interval boundary) and return the round's opponent counts."""
-        counts = self._counts.cpu().tolist()
+        counts = self._counts[0].cpu().tolist()
         out = {"strong": counts[0], "weak": counts[1], "self_play": counts[2]}
         if self.pool is not None:
             if self.bank is not None:
@@ -274,7 +298,7 @@ class PopulationOpponentMix:
     GPU once the bank exceeds 64 slots).  The curriculum row is shared: the members share ``curriculum_name``
     (``curriculum``: a name or a table, default the first member's).
 
-    The bot-or-self-play draws are ``OpponentMix._select_arena``'s, from one generator over the population (seeded
+    The bot-or-self-play draws are ``OpponentMix``'s (``_draw``), from one generator over the population (seeded
     by the first member's seed); an arena can draw self-play only if its member uses it and that member's pool
     holds a snapshot, otherwise it falls through to the bots.  sampling="arena": every arena draws its snapshot from
     its own member's scores (one 2-D ``torch.multinomial`` over the [S, Pmax] score matrix; empty rows carry a dummy
@@ -304,6 +328,9 @@ class PopulationOpponentMix:
             from .policy_bank import PolicyBank
 
             self.bank = PolicyBank(self.S * self.stride, dev, wide=True)
+            for p in self.pools:
+                if p is not None:
+                    p.bank = self.bank  # the pool frees its dropped snapshots' slots; snapshot() picks the new ones
         self.gen = torch.Generator(device=dev)
         self.gen.manual_seed(seeds[0] + 0x5EED)
         self.p_strong, self.p_weak, self.p_self = 0.0, 1.0, 0.0
@@ -326,20 +353,9 @@ class PopulationOpponentMix:
             pool = self.pools[j]
             if pool is None:
                 raise ValueError(f"member {j} does not use self-play")
-            snap = copy.deepcopy(actor).eval()
-            for p in snap.parameters():
-                p.requires_grad_(False)
             lo = j * self.stride
-            slot = next(k for k in range(lo, lo + pool.pool_size + 1) if k not in pool.slots)
-            pool.pool.append(snap)
-            pool.scores.append(1.0)
-            pool.slots.append(slot)
-            if len(pool.pool) > pool.pool_size:
-                pool.pool.pop(0)
-                pool.scores.pop(0)
-                self.bank.free(pool.slots.pop(0))
-            slots.append(slot)
-            snaps.append(snap)
+            slots.append(next(k for k in range(lo, lo + pool.pool_size + 1) if k not in pool.slots))
+            snaps.append(pool.add_snapshot(actor, slots[-1]))
         if slots:
             self.bank.replace_many(slots, snaps)
 
@@ -377,19 +393,10 @@ class PopulationOpponentMix:
         """(policy2 [N] uint8, actions [N, 8] or None, bank slot per arena [N] int32 or None) for this step.  The
         self-play arenas' player-2 actions are written into ``out[:, 4:8]`` (``out``: the caller's [N, 8] action
         buffer, or one kept here); every other float of it is left alone."""
-        n, dev, S = self.n, self.device, self.S
+        n, S = self.n, self.S
         scores, slots, have = self._pool_tensors()
-        u_sp = torch.rand(n, device=dev, generator=self.gen)
-        u_bot = torch.rand(n, device=dev, generator=self.gen)
-        sp = (u_sp < self.p_self) & have[self.member_of]
-        strong = ~sp & (u_bot < self.p_strong)
-        weak = ~sp & ~strong
-        p2 = self._policy2
-        p2.fill_(N.POLICY_BASIC_WEAK)
-        p2.masked_fill_(strong, N.POLICY_BASIC_STRONG)
-        p2.masked_fill_(sp, N.POLICY_EXTERNAL)
-        self._counts += torch.stack([strong.view(S, -1).sum(1), weak.view(S, -1).sum(1), sp.view(S, -1).sum(1)], 1)
-        self._sp_mask, self._snap = sp, None
+        sp = _draw(self, have[self.member_of])
+        p2, self._snap = self._policy2, None
         if not self._any:
             return p2, None, None
         if self.sampling == "arena":  # pool index per arena, from the arena's own member's scores
@@ -397,11 +404,7 @@ class PopulationOpponentMix:
         else:  # one per member and step
             snap = torch.multinomial(scores, 1, generator=self.gen).expand(S, self.n_per).reshape(n)
         policy = torch.where(sp, slots[self.member_of, snap], self._minus1)
-        if out is None:
-            if getattr(self, "_act8", None) is None:
-                self._act8 = torch.zeros((n, 8), dtype=torch.float32, device=dev)
-            out = self._act8
-        self.bank.act(obs2, policy, out=out, out_col=4, backend=self.backend)
+        out = _bank_act(self, obs2, policy, out)
         self._snap = self.member_of * self.pmax + snap  # the (member, snapshot) each arena faces, flat
         self._snap_counts.scatter_add_(0, self._snap, sp.to(torch.int64))
         return p2, out, policy
@@ -409,14 +412,8 @@ class PopulationOpponentMix:
     def register_outcomes(self, done, reward):
         """Done steps of this step's self-play arenas, charged to the (member, snapshot) the arena faced: agent win
         (reward > 0) or not.  Tallied on the device; end_round() applies the steps in order."""
-        if self._snap is None:
-            return
-        d = (done != 0) & self._sp_mask
-        win = d & (reward > 0)
-        tally = torch.zeros((self.S * self.pmax, 2), dtype=torch.int64, device=self.device)
-        tally[:, 0].scatter_add_(0, self._snap, win.to(torch.int64))
-        tally[:, 1].scatter_add_(0, self._snap, (d & ~win).to(torch.int64))
-        self._outcomes.append(tally)
+        if self._snap is not None:
+            self._outcomes.append(_tally(self, done, reward, self.S * self.pmax))
 
     def end_round(self, actors=None, episodes=0):
         """Per member: fold the round's outcomes, in step order, through its pool's ``update_difficulty``, advance its
@@ -439,14 +436,7 @@ class PopulationOpponentMix:
                     pool.update_difficulty(i, int(steps[t, idx, 0]), int(steps[t, idx, 1]))
         if actors is not None:
             eps = list(episodes) if isinstance(episodes, (list, tuple)) else [episodes] * S
-            crossed = []
-            for j, pool in enumerate(self.pools):
-                if pool is None or not eps[j]:
-                    continue
-                before = pool.episode_counter // pool.interval
-                pool.episode_counter += int(eps[j])
-                if pool.episode_counter // pool.interval > before:
-                    crossed.append(j)
+            crossed = [j for j, pool in enumerate(self.pools) if pool is not None and eps[j] and pool.advance(eps[j])]
             self.snapshot(crossed, [actors[j] for j in crossed])
         self.reset_stats()
         return out

@@ -21,8 +21,8 @@ import ctypes
 import torch
 
 from . import _native
-from .learner_hip import (ACT_MAX_POLICIES, ACT_PARAM_FLOATS, ACT_WIDE_MAX_POLICIES, PACK_FLOATS, ActIO, ActWideIO, Net,
-                          act_wide_max_tiles)
+from .learner_hip import (ACT_MAX_POLICIES, ACT_PARAM_FLOATS, ACT_WIDE_MAX_POLICIES, GROUP_MAX, PACK_FLOATS, ActIO,
+                          ActWideIO, Net, PackIO, act_wide_max_tiles, check, lib, stream_ptr, upload)
 
 # floats of fc1.weight, fc1.bias, fc2.weight, fc2.bias, fc3.weight, fc3.bias inside a slot (torch layout, this order)
 _SHAPES = (("fc1.weight", (256, 18)), ("fc1.bias", (256,)), ("fc2.weight", (256, 256)), ("fc2.bias", (256,)),
@@ -131,14 +131,9 @@ class PolicyBank:
         return {name: row[o:o + n].view(shape) for name, (o, n, shape) in _OFF.items()}
 
     # ------------------------------------------------------------------ hip
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _pack(self, slots):
         """Refresh the operand packs of ``slots``: one ``hkl_pack`` for up to its 4 networks, else one
         ``hkl_pack_group`` launch per 64 slots (one network per member of the group, no step counter)."""
-        from .learner_hip import GROUP_MAX, PackIO, _check, lib
-
         if self._packs is None:
             self._packs = torch.zeros((self.capacity, PACK_FLOATS), dtype=torch.float32, device=self.device)
         base, pbase = self.params.data_ptr(), self._packs.data_ptr()
@@ -148,20 +143,18 @@ class PolicyBank:
             p = [ctypes.c_void_p(b + 4 * _OFF[name][0]) for name, _ in _SHAPES]
             nets.append(Net(p[0], p[1], p[2], p[3], p[4], p[5], ctypes.c_void_p(pbase + 4 * PACK_FLOATS * slot), 18, 4))
         if len(nets) <= 4:
-            _check(lib().hkl_pack((Net * len(nets))(*nets), len(nets), None, self._stream()), "hkl_pack")
+            check(lib().hkl_pack((Net * len(nets))(*nets), len(nets), None, stream_ptr(self.device)), "hkl_pack")
             return
         for lo in range(0, len(nets), GROUP_MAX):
             chunk = nets[lo:lo + GROUP_MAX]
             ios = (PackIO * len(chunk))()
             for io, net in zip(ios, chunk):
                 io.net[0] = net
-            dev = torch.frombuffer(bytearray(ios), dtype=torch.uint8).to(self.device)  # the same bytes on the device
-            _check(lib().hkl_pack_group(ios, ctypes.c_void_p(dev.data_ptr()), 1, len(chunk), self._stream()),
-                   "hkl_pack_group")
+            dev = upload(ios, self.device)
+            check(lib().hkl_pack_group(ios, ctypes.c_void_p(dev.data_ptr()), 1, len(chunk), stream_ptr(self.device)),
+                  "hkl_pack_group")
 
     def _act_hip(self, obs, policy, out, out_col, base_slot=0):
-        from .learner_hip import _check, lib
-
         L = lib()
         if self.device.type != "cuda":
             raise _native.HockeyNativeError("PolicyBank backend='hip' runs on the GPU only")
@@ -196,9 +189,9 @@ class PolicyBank:
             else:
                 io.order, io.counts, io.offsets = (t.data_ptr() for t in sc)
         if wide:
-            _check(L.hkl_act_wide(ctypes.byref(io), self._stream()), "hkl_act_wide")
+            check(L.hkl_act_wide(ctypes.byref(io), stream_ptr(self.device)), "hkl_act_wide")
         else:
-            _check(L.hkl_act(ctypes.byref(io), self._stream()), "hkl_act")
+            check(L.hkl_act(ctypes.byref(io), stream_ptr(self.device)), "hkl_act")
 
     # ------------------------------------------------------------------ torch (the reference path)
     def _forward_torch(self, slot, x):

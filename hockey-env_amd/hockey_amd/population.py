@@ -25,15 +25,13 @@ its position in the population and on who else is in it.
 """
 import ctypes
 
-import numpy as np
 import torch
 
+from . import learner_hip as LH
 from .constants import Mode
-from .evaluate import reset_params
+from .learner_hip import GROUP_MAX
 from .noise import make_noise
-from .td3 import TD3, Learner, ReplayRing, updates_for
-
-GROUP_MAX = 64  # HKL_GROUP_MAX
+from .td3 import TD3, Learner, PairRunner, PerBlocks, ReplayRing, RoundClock, reset_round, store_step, updates_for
 
 
 # ---------------------------------------------------------------------------------------------------- replay
@@ -139,11 +137,11 @@ class PopulationPrioritizedRing(PopulationRing):
     stores to ``w`` itself calls ``refresh()`` afterwards."""
 
     def __init__(self, S, capacity, prioritized=None, beta=0.15, init_weight=1e8, device="cuda:0", n_obs=18, n_act=4):
-        from . import _native, learner_hip as LH
+        from . import _native
 
         if torch.device(device).type != "cuda":
             raise _native.HockeyNativeError("the device prioritized replay sampler runs on the GPU only")
-        self._LH, self._L = LH, LH.lib()
+        self._L = LH.lib()
         S = int(S)
         self.prioritized = [True] * S if prioritized is None else [bool(x) for x in prioritized]
         self.beta = [float(x) for x in (beta if isinstance(beta, (list, tuple)) else [beta] * S)]
@@ -153,14 +151,8 @@ class PopulationPrioritizedRing(PopulationRing):
             raise ValueError(f"a population has 1 to {GROUP_MAX} members, got {S}")
         cap = int(capacity)
         d = torch.device(device)
-        nb = self.nblk = -(-cap // self._L.hkl_per_block())
         self.wstride = -(-cap // 4) * 4
         self.w = torch.full((S * self.wstride,), float(init_weight), device=d)
-        self.bsum = torch.zeros(S * nb, dtype=torch.float64, device=d)
-        self.bpre = torch.zeros(S * nb, dtype=torch.float64, device=d)
-        self.bmax = torch.zeros(S * nb, dtype=torch.float32, device=d)
-        self.last = torch.zeros(S * cap, dtype=torch.int32, device=d)
-        self.bown = torch.zeros(S * nb, dtype=torch.int32, device=d)
         self.pers = None
         super().__init__(S, cap, device=d, n_obs=n_obs, n_act=n_act)  # builds the members through _make_member
         # the push's device arguments: fixed buffers, so that the launch reads what this push computed
@@ -168,23 +160,17 @@ class PopulationPrioritizedRing(PopulationRing):
         self.refresh()
 
     def _make_member(self, j):
-        if self.pers is None:
-            LH, nb, cap = self._LH, self.nblk, self.cap
-            at = lambda t, i: ctypes.c_void_p(t.data_ptr() + i * t.element_size())  # noqa: E731
-            self.pers = (LH.Per * self.S)(*[
-                LH.Per(cap, at(self.w, k * self.wstride), at(self.size_t, k), at(self.bsum, k * nb),
-                       at(self.bmax, k * nb), at(self.bpre, k * nb), at(self.last, k * cap), at(self.bown, k * nb))
-                for k in range(self.S)])
-            self._pers_dev = _upload(self.pers, self.device)
+        if self.pers is None:  # the first member: the fill levels exist by now
+            blk = self._blocks = PerBlocks(self.S, self.cap, self.w, self.wstride, self.size_t)
+            self.nblk, self.pers = blk.nblk, blk.pers
+            self.bsum, self.bpre, self.bmax, self.last, self.bown = blk.buffers
+            self._pers_dev = LH.upload(self.pers, self.device)
         return _MemberPrioritizedRing(self, j) if self.prioritized[j] else _MemberRing(self, j)
-
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def refresh(self):
         """Recompute every member's block sums and maxima from ``w`` and the fill levels."""
-        self._LH._check(self._L.hkl_per_refresh_group(self.pers, self._pers_dev.data_ptr(), self.S, self._stream()),
-                        "hkl_per_refresh_group")
+        LH.check(self._L.hkl_per_refresh_group(self.pers, self._pers_dev.data_ptr(), self.S,
+                                               LH.stream_ptr(self.device)), "hkl_per_refresh_group")
 
     def _before_commit(self, counts, n):
         # hkl_per_push per member, before the fill levels change: the pushed blocks' sums are taken against the
@@ -194,18 +180,13 @@ class PopulationPrioritizedRing(PopulationRing):
         a[1].copy_(counts)
         torch.clamp(self.size_t + counts, max=self.cap, out=a[2])
         p = a.data_ptr()
-        self._LH._check(self._L.hkl_per_push_group(self.pers, self._pers_dev.data_ptr(), p, p + 8 * self.S,
-                                                   p + 16 * self.S, min(int(n), self.cap), self.S, self._stream()),
-                        "hkl_per_push_group")
+        LH.check(self._L.hkl_per_push_group(self.pers, self._pers_dev.data_ptr(), p, p + 8 * self.S, p + 16 * self.S,
+                                            min(int(n), self.cap), self.S, LH.stream_ptr(self.device)),
+                 "hkl_per_push_group")
 
 
 # ---------------------------------------------------------------------------------------------------- learner
-def _upload(arr, device):
-    """The bytes of a ctypes array in device memory (uint8 tensor; the allocator's alignment exceeds any struct's)."""
-    return torch.frombuffer(bytearray(arr), dtype=torch.uint8).to(device)
-
-
-class PopulationLearner:
+class PopulationLearner(PairRunner):
     """Learner updates of S = len(agents) <= 64 TD3 agents, agent j on rings[j], at batch ``batch`` in the launches
     one agent takes (module docstring).  rng is "device" only: each member's slots and target noise come from its own
     Philox stream, keyed by its agent's seed.  Members may differ in seed, lr_q, lr_pol, wd_*, gamma, tau_* and the
@@ -245,11 +226,9 @@ class PopulationLearner:
             self.eager = [Learner(ag, rg, self.B, graphs=False, fused=False) for ag, rg in zip(self.agents, self.rings)]
             self.use_graph = False
             return
-        from . import learner_hip as LH
-
         self.eager = None
         self.use_graph = bool(graphs)
-        self.LH, self.L = LH, LH.lib()
+        self.L = LH.lib()
         self.members = [LH.FusedLearner(ag, rg, self.B, rng="device") for ag, rg in zip(self.agents, self.rings)]
         self.acc = torch.zeros((S, 4), dtype=torch.float64, device=self.device)  # per member: Learner.acc
         for j, f in enumerate(self.members):
@@ -258,7 +237,7 @@ class PopulationLearner:
 
     def _gather(self):
         """The members' io structs as host arrays (kept: the grouped calls check them) and their device copies."""
-        LH, S, ms = self.LH, self.S, self.members
+        S, ms = self.S, self.members
         h = {"cio": (LH.CriticIO * S)(*[f.cio for f in ms]),
              "aio": (LH.ActorIO * S)(*[f.aio for f in ms]), "adam_a": (LH.AdamIO * S)(*[f.adam["actor"] for f in ms])}
         # the batch's slots: hkl_sample_group over the uniform members, hkl_per_sample_group over the prioritized
@@ -294,7 +273,7 @@ class PopulationLearner:
             pa[j].step = f.step["actor"].data_ptr()
         h["pack_c"], h["pack_a"] = pc, pa
         self.host = h
-        self.dev = {k: _upload(v, self.device) for k, v in h.items()}
+        self.dev = {k: LH.upload(v, self.device) for k, v in h.items()}
         self.dptr = {k: ctypes.c_void_p(v.data_ptr()) for k, v in self.dev.items()}
 
     # ------------------------------------------------------------------ one update
@@ -304,8 +283,8 @@ class PopulationLearner:
             for lr in self.eager:
                 lr._one(bool(train_actor))
             return
-        L, S, B, h, ck = self.L, self.S, self.B, self.host, self.LH._check
-        st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        L, S, B, h, ck = self.L, self.S, self.B, self.host, LH.check
+        st = LH.stream_ptr(self.device)
         d = self.dptr
         if self.n_uniform:
             ck(L.hkl_sample_group(h["sio"], d["sio"], self.n_uniform, st), "hkl_sample_group")
@@ -333,38 +312,11 @@ class PopulationLearner:
         self.update(False)
         self.update(True)
 
-    def _sync_steps(self):
-        for ag in self.agents:
-            ag.train_step = self.train_step
-
     def run(self, k):
         """k updates of every member (hockey_amd.td3.Learner.run: graph replay of update pairs after the warm-up)."""
-        k = int(k)
-        if not self.use_graph or self.train_step % 2:
-            for _ in range(k):
-                self._one()
-            return self._sync_steps()
-        pairs, rest = divmod(k, 2)
-        dev = self.device
-        for _ in range(pairs):
-            if self.graph is not None:
-                self.graph.replay()
-            elif self.warm_left > 0:  # eager warm-up pairs on a side stream (graph capture prerequisite)
-                st = torch.cuda.Stream(dev)
-                st.wait_stream(torch.cuda.current_stream(dev))
-                with torch.cuda.stream(st):
-                    self._pair()
-                torch.cuda.current_stream(dev).wait_stream(st)
-                self.warm_left -= 1
-            else:
-                self.graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph):
-                    self._pair()
-                self.graph.replay()  # capture records without running: this replay is the pair's update
-            self.train_step += 2
-        for _ in range(rest):
-            self._one()
-        self._sync_steps()
+        self._run_pairs(k, self, self.device)  # the count is this learner's own, mirrored to the agents afterwards
+        for ag in self.agents:
+            ag.train_step = self.train_step
 
     def take_losses(self):
         """[(mean critic loss, mean actor loss)] per member since the last call (None without updates)."""
@@ -449,8 +401,6 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
     member.  A member's trajectory therefore
     depends on its position in the population and on its size; only the learner is composition-independent (module
     docstring)."""
-    import time
-
     from .opponents import OpponentMix, PopulationOpponentMix
     from .policy_bank import PolicyBank
 
@@ -512,21 +462,21 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
     if self_play is not None:
         for st in stats:
             st["pool_size"] = []
-    episodes, next_eval = 0, c0.eval_interval
+    episodes = 0
     stop_at_done = episode_end == "done"
-    sync = (lambda: torch.cuda.synchronize(dev)) if timing else (lambda: None)
+    clock = RoundClock(dev, timing, c0.eval_interval)
+    all_rows = torch.arange(N, device=dev)
+
+    def store(rows, res, *row):  # ragged over the members
+        m = member_of if rows is None else member_of[rows]
+        ring.push(m, *row)
+        if on_step is not None:
+            on_step(m, all_rows if rows is None else rows, *row, res)
+
     for rnd in range(rounds):
-        sync()
-        t0 = time.perf_counter()
+        clock.start()
         mix.update_schedule((episodes + 1) / (rounds * n))
-        e = np.arange(rnd * n, (rnd + 1) * n, dtype=np.int64)  # the round's episodes of one member, 0-based
-        if hasattr(env, "reset_seeded"):
-            seeds = torch.cat([torch.arange(seed + 1 + rnd * n, seed + 1 + (rnd + 1) * n) for _, seed, _ in ms])
-            obs, obs2 = (t.clone() for t in env.reset_seeded(seeds.to(env.device), one_starting=np.tile((e % 2) == 1, S)))
-        else:
-            p = np.concatenate([reset_params(n, seed + rnd * n + 1, mode, first_reset=rnd * n)[0] for _, seed, _ in ms])
-            env.reset_params(p)
-            obs, obs2 = (t.clone() for t in env.observe())
+        obs, obs2 = reset_round(env, "seeded", mode, rnd, n, [seed for _, seed, _ in ms])
         for g, _, _ in gens.values():
             g.reset()
         ep_reward = torch.zeros(N, device=dev)
@@ -565,23 +515,11 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
             o2, r, d = res.obs.clone(), res.reward.clone(), res.done.clone()
             for j in range(S):
                 round_steps[j] += n_alive[j]
-            if stop_at_done:  # only the transitions of episodes that were still running are stored
-                idx = torch.nonzero(alive).squeeze(1)
-                ring.push(member_of[idx], obs[idx], a[idx], r[idx], o2[idx], d[idx])
-                if on_step is not None:
-                    on_step(member_of[idx], idx, obs[idx], a[idx], r[idx], o2[idx], d[idx], res)
-                mix.register_outcomes(d & alive, r)
-                ep_reward += torch.where(alive, r, torch.zeros_like(r))
-                alive &= d == 0
+            store_step(store, mix, stop_at_done, alive, ep_reward, res, obs, a, r, o2, d)
+            if stop_at_done:
                 n_alive = alive.view(S, n).sum(1).tolist()  # the step's one host sync, as train's
                 if not any(n_alive):
                     break
-            else:
-                ring.push(member_of, obs, a, r, o2, d)
-                if on_step is not None:
-                    on_step(member_of, torch.arange(N, device=dev), obs, a, r, o2, d, res)
-                mix.register_outcomes(d, r)
-                ep_reward += r
             obs, obs2 = o2, res.obs2.clone()
         episodes += n
         if self_play is None:
@@ -596,8 +534,7 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
             if self_play is not None:
                 stats[j]["pool_size"].append(mix.pool_sizes()[j])
             stats[j]["noise_scale"].append(agents[j].current_noise_scale)
-        sync()
-        t1 = time.perf_counter()
+        clock.collected()
         if all(ag.total_steps > batch for ag in agents):
             learner.run(updates)
             for j, (cl, al) in enumerate(learner.take_losses()):
@@ -610,14 +547,10 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
         else:
             for st in stats:
                 st["skipped_rounds"] += 1
-        sync()
-        if timing:
-            for st in stats:
-                st["round_time"].append((t1 - t0, time.perf_counter() - t1))
-        if eval_fn is not None and episodes >= next_eval:
+        clock.updated(stats)
+        if eval_fn is not None and clock.eval_due(episodes):
             for j, ag in enumerate(agents):
                 stats[j]["evals"].append(eval_fn(ag, episodes))
-            next_eval = (episodes // c0.eval_interval + 1) * c0.eval_interval
         if log:
             log(rnd, stats)
     if own_env:

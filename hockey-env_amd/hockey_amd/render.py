@@ -13,6 +13,7 @@ import os
 import torch
 
 from . import _native
+from .learner_hip import stream_ptr
 
 LIB_PATH = os.environ.get("HK_RENDER_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib",
                                                            "libhockey_render.so")
@@ -76,10 +77,9 @@ def render_states(state, idx=None, height=NATIVE_HEIGHT, width=NATIVE_WIDTH, for
     if m == 0:
         return out
     with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         rc = lib().hkr_render(_native.ptr(state), state.shape[0], _native.ptr(idx), m, int(height), int(width),
                               _FORMATS[format], STATIC_ONLY if static_only else 0, _native.ptr(out),
-                              _native.ptr(bad_index_count), stream)
+                              _native.ptr(bad_index_count), stream_ptr(dev))
     if rc != 0:
         raise _native.HockeyNativeError(f"hkr_render failed ({rc}): {lib().hkr_last_error().decode()}")
     return out

@@ -34,6 +34,7 @@ the reference's replay ratio (samples drawn per stored transition, ``train_iters
 """
 import json
 import math
+import time
 from dataclasses import dataclass, fields
 
 import numpy as np
@@ -269,6 +270,26 @@ class PrioritizedRing(ReplayRing):
         self.w[slot] = torch.clamp(td.detach()[perm[end]], 1e-6, 1e6)
 
 
+class PerBlocks:
+    """The device sampler's state beside the weights, for S >= 1 rings of ``cap`` slots whose weights start
+    ``wstride`` floats apart in ``w`` and whose fill levels are the S int64 of ``size_t``: ``buffers`` = (bsum, bpre
+    float64 [S * nblk], bmax float32 [S * nblk], last int32 [S * cap], bown int32 [S * nblk]) with ``nblk`` blocks of
+    ``hkl_per_block()`` slots per ring, and ``pers``, one ``Per`` struct per ring onto its slices (a ctypes array).
+    DevicePrioritizedRing (S = 1) and hockey_amd.population.PopulationPrioritizedRing are built on it."""
+
+    def __init__(self, S, cap, w, wstride, size_t):
+        import ctypes
+        from . import learner_hip as LH
+        nb = self.nblk = -(-cap // LH.lib().hkl_per_block())
+        self.buffers = tuple(torch.zeros(S * n, dtype=dt, device=w.device) for n, dt in (
+            (nb, torch.float64), (nb, torch.float64), (nb, torch.float32), (cap, torch.int32), (nb, torch.int32)))
+        bsum, bpre, bmax, last, bown = self.buffers
+        at = lambda t, i: ctypes.c_void_p(t.data_ptr() + i * t.element_size())  # noqa: E731
+        self.pers = (LH.Per * S)(*[
+            LH.Per(cap, at(w, k * wstride), at(size_t, k), at(bsum, k * nb), at(bmax, k * nb), at(bpre, k * nb),
+                   at(last, k * cap), at(bown, k * nb)) for k in range(S)])
+
+
 class DevicePrioritizedRing(PrioritizedRing):
     """PrioritizedRing whose push, sampling, importance weights and priority write-back run through the hkl_per_*
     kernels (include/hockey_learner.h, csrc/hkl_per.h) on float64 sums per block of ``hkl_per_block()`` slots,
@@ -286,40 +307,31 @@ class DevicePrioritizedRing(PrioritizedRing):
         self._LH, self._L = LH, LH.lib()
         super().__init__(capacity, n_obs, n_act, device, beta, init_weight)
         self._slot = None  # the whole-ring passes' arange: not needed here
-        d = self.device
-        nblk = -(-self.cap // self._L.hkl_per_block())
-        self._bsum = torch.zeros(nblk, dtype=torch.float64, device=d)
-        self._bpre = torch.zeros(nblk, dtype=torch.float64, device=d)
-        self._bmax = torch.zeros(nblk, dtype=torch.float32, device=d)
-        self._last = torch.zeros(self.cap, dtype=torch.int32, device=d)
-        self._bown = torch.zeros(nblk, dtype=torch.int32, device=d)
-        p = LH._p
-        self.per = LH.Per(self.cap, p(self.w), p(self.size_t), p(self._bsum), p(self._bmax), p(self._bpre),
-                          p(self._last), p(self._bown))
+        self._blocks = PerBlocks(1, self.cap, self.w, self.cap, self.size_t)
+        self._bsum, self._bpre, self._bmax, self._last, self._bown = self._blocks.buffers
+        self.per = self._blocks.pers[0]
         self.iw = None
         self.refresh()
-
-    def _stream(self):
-        import ctypes
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def refresh(self, lo=0, n=None):
         """Recompute the block sums that cover slots [lo, lo + n) (default: all) from ``w`` and the fill level."""
         n = self.cap - lo if n is None else n
-        self._LH._check(self._L.hkl_per_refresh(self.per, lo, n, self._stream()), "hkl_per_refresh")
+        LH = self._LH
+        LH.check(self._L.hkl_per_refresh(self.per, lo, n, LH.stream_ptr(self.device)), "hkl_per_refresh")
 
     def _before_push(self, n):
         # the pushed blocks' sums are taken against the new fill level, which ReplayRing.push stores afterwards
         if n > 0:
-            self._LH._check(self._L.hkl_per_push(self.per, self.pos, n, min(self.size + n, self.cap),
-                                                 self._stream()), "hkl_per_push")
+            LH = self._LH
+            LH.check(self._L.hkl_per_push(self.per, self.pos, n, min(self.size + n, self.cap),
+                                          LH.stream_ptr(self.device)), "hkl_per_push")
 
     def _draw(self, batch, u):
         LH = self._LH
         idx = torch.empty(batch, dtype=torch.int64, device=self.device)
         iw = torch.empty(batch, dtype=torch.float32, device=self.device)
-        io = LH.PerSampleIO(self.per, batch, 0, None, LH._p(u), LH._p(idx), None, 0.0, 0.0, LH._p(iw), self.beta)
-        LH._check(self._L.hkl_per_sample(io, self._stream()), "hkl_per_sample")
+        io = LH.PerSampleIO(self.per, batch, 0, None, LH.ptr(u), LH.ptr(idx), None, 0.0, 0.0, LH.ptr(iw), self.beta)
+        LH.check(self._L.hkl_per_sample(io, LH.stream_ptr(self.device)), "hkl_per_sample")
         self.last, self.iw = idx, iw
         return idx
 
@@ -334,8 +346,8 @@ class DevicePrioritizedRing(PrioritizedRing):
         LH = self._LH
         i = self.last.contiguous()
         td = td.detach().float().contiguous()
-        io = LH.PerUpdateIO(self.per, i.numel(), LH._p(i), LH._p(td))
-        LH._check(self._L.hkl_per_update(io, self._stream()), "hkl_per_update")
+        io = LH.PerUpdateIO(self.per, i.numel(), LH.ptr(i), LH.ptr(td))
+        LH.check(self._L.hkl_per_update(io, LH.stream_ptr(self.device)), "hkl_per_update")
 
 
 class TD3:
@@ -515,7 +527,45 @@ def fused_available():
     return os.path.exists(LIB_PATH)
 
 
-class Learner:
+class PairRunner:
+    """The update-pair state machine of Learner and hockey_amd.population.PopulationLearner.  A subclass sets
+    ``use_graph``, ``warm_left`` and ``graph`` (None) and gives ``_one()``, one update that counts itself, and
+    ``_pair()``, a critic-only update and then one with the actor, uncounted."""
+
+    def _run_pairs(self, k, counter, device, before_capture=None):
+        """k updates.  ``counter.train_step`` is the update count ``_one`` advances; here it advances by 2 per pair.
+        Without graphs, or from an odd count, every update is a ``_one``.  Else pairs: the first ``warm_left`` run
+        eagerly on a side stream (graph capture's prerequisite), the next is captured (after ``before_capture()``)
+        and replayed, the later ones replay it; an odd last update is a ``_one``."""
+        k = int(k)
+        if not self.use_graph or counter.train_step % 2:
+            for _ in range(k):
+                self._one()
+            return
+        pairs, rest = divmod(k, 2)
+        for _ in range(pairs):
+            if self.graph is not None:
+                self.graph.replay()
+            elif self.warm_left > 0:  # eager warm-up pairs on a side stream (graph capture prerequisite)
+                st = torch.cuda.Stream(device)
+                st.wait_stream(torch.cuda.current_stream(device))
+                with torch.cuda.stream(st):
+                    self._pair()
+                torch.cuda.current_stream(device).wait_stream(st)
+                self.warm_left -= 1
+            else:
+                self.graph = torch.cuda.CUDAGraph()
+                if before_capture is not None:
+                    before_capture()
+                with torch.cuda.graph(self.graph):
+                    self._pair()
+                self.graph.replay()  # capture records without running: this replay is the pair's update
+            counter.train_step += 2
+        for _ in range(rest):
+            self._one()
+
+
+class Learner(PairRunner):
     """Runs ``k`` learner updates (sample + learner.update) of ``agent`` on ``ring``.
 
     With ``graphs`` on a GPU the pair (critic update; critic + delayed actor + Polyak) is captured once as a HIP
@@ -562,40 +612,86 @@ class Learner:
         self._one(False)
         self._one(True)
 
+    def _zero_grads(self):  # before capture: the eager optimisers' gradients are allocated inside the graph
+        self.agent.opt_critic.zero_grad(set_to_none=True)
+        self.agent.opt_actor.zero_grad(set_to_none=True)
+
     def run(self, k):
-        ag = self.agent
-        k = int(k)
-        if not self.use_graph or ag.train_step % 2:
-            for _ in range(k):
-                self._one()
-            return
-        pairs, rest = divmod(k, 2)
-        for _ in range(pairs):
-            if self.graph is not None:
-                self.graph.replay()
-            elif self.warm_left > 0:  # eager warm-up pairs on a side stream (graph capture prerequisite)
-                st = torch.cuda.Stream(ag.device)
-                st.wait_stream(torch.cuda.current_stream(ag.device))
-                with torch.cuda.stream(st):
-                    self._pair()
-                torch.cuda.current_stream(ag.device).wait_stream(st)
-                self.warm_left -= 1
-            else:
-                self.graph = torch.cuda.CUDAGraph()
-                ag.opt_critic.zero_grad(set_to_none=True)
-                ag.opt_actor.zero_grad(set_to_none=True)
-                with torch.cuda.graph(self.graph):
-                    self._pair()
-                self.graph.replay()  # capture records without running: this replay is the pair's update
-            ag.train_step += 2
-        for _ in range(rest):
-            self._one()
+        self._run_pairs(k, self.agent, self.agent.device, self._zero_grads)
 
     def take_losses(self):
         """Mean critic / actor loss since the last call (one host sync)."""
         s = self.acc.cpu().tolist()
         self.acc.zero_()
         return (s[0] / s[2] if s[2] else None), (s[1] / s[3] if s[3] else None)
+
+
+def reset_round(env, reset, mode, rnd, n, seeds):
+    """(obs, obs2) after resetting ``env`` for round ``rnd`` of ``train`` / ``train_population``: one block of ``n``
+    arenas per entry of ``seeds``, whose arena i plays episode e = rnd * n + i + 1 of that seed's run, placed like
+    ``reset(seed=seed + e)`` with the puck side toggling per reset.  reset: "seeded" (drawn by the kernel where the
+    env has ``reset_seeded``, else on the host), "seeded_host", or "device" (the kernel's Philox placement)."""
+    if reset == "device":
+        pair = env.reset()
+    elif reset == "seeded" and hasattr(env, "reset_seeded"):
+        # the same episodes as below, drawn by the kernel: seeds and puck sides are reset_params' own
+        e = np.arange(rnd * n, (rnd + 1) * n, dtype=np.int64)
+        st = torch.cat([torch.arange(s + 1 + rnd * n, s + 1 + (rnd + 1) * n, device=env.device) for s in seeds])
+        pair = env.reset_seeded(st, one_starting=np.tile((e % 2) == 1, len(seeds)))
+    else:
+        env.reset_params(np.concatenate([reset_params(n, s + rnd * n + 1, mode, first_reset=rnd * n)[0]
+                                         for s in seeds]))
+        pair = env.observe()
+    return tuple(t.clone() for t in pair)
+
+
+def store_step(store, mix, stop_at_done, alive, ep_reward, res, obs, a, r, o2, d):
+    """A collection step's bookkeeping for both ``episode_end`` values: ``store(rows, res, obs, a, r, o2, d)`` gets
+    the transitions to keep (rows: their arena indices, or None for all arenas), ``mix`` the step's outcomes, and
+    ``ep_reward`` the rewards.  episode_end="done" keeps only the arenas still ``alive`` and clears the flag of those
+    that ended (in place); the caller counts the survivors."""
+    if stop_at_done:  # only the transitions of episodes that were still running are stored
+        idx = torch.nonzero(alive).squeeze(1)
+        store(idx, res, obs[idx], a[idx], r[idx], o2[idx], d[idx])
+        mix.register_outcomes(d & alive, r)
+        ep_reward += torch.where(alive, r, torch.zeros_like(r))
+        alive &= d == 0
+    else:
+        store(None, res, obs, a, r, o2, d)
+        mix.register_outcomes(d, r)
+        ep_reward += r
+
+
+class RoundClock:
+    """A training round's wall-clock marks (with ``timing``: a device synchronise before each) and the evaluation
+    schedule, every ``eval_interval`` episodes."""
+
+    def __init__(self, device, timing, eval_interval):
+        self.device, self.timing, self.interval, self.next_eval = device, timing, eval_interval, eval_interval
+
+    def mark(self):
+        if self.timing:
+            torch.cuda.synchronize(self.device)
+        return time.perf_counter()
+
+    def start(self):
+        self.t0 = self.mark()
+
+    def collected(self):
+        self.t1 = self.mark()
+
+    def updated(self, stats):
+        """Append (collection seconds, update seconds) to every dict's "round_time" (with ``timing``)."""
+        t2 = self.mark()
+        if self.timing:
+            for st in stats:
+                st["round_time"].append((self.t1 - self.t0, t2 - self.t1))
+
+    def eval_due(self, episodes):
+        due = episodes >= self.next_eval
+        if due:
+            self.next_eval = (episodes // self.interval + 1) * self.interval
+        return due
 
 
 def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_per_round=None, mode=Mode.NORMAL,
@@ -641,7 +737,6 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
     "arena" draws one per arena and step, played through a PolicyBank in one call (hockey_amd.opponents); the
     round's ``stats["opponents"]`` entry then also lists the arena-steps per snapshot.  mix: a ready OpponentMix
     for ``n_arenas`` on ``device`` to use instead of building one (a pool carried over from an earlier run)."""
-    import time
     from .opponents import OpponentMix
     from .vec_env import VecHockeyEnv
 
@@ -682,27 +777,20 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
              "replay_capacity": cap, "critic_loss": [], "actor_loss": [], "mean_reward": [], "opponents": [],
              "pool_size": [], "evals": [], "round_time": []}
     episodes = 0
-    next_eval = cfg.eval_interval
     if episode_end not in ("max_steps", "done"):
         raise ValueError("episode_end must be 'max_steps' or 'done'")
     stop_at_done = episode_end == "done"
-    sync = (lambda: torch.cuda.synchronize(device)) if timing else (lambda: None)
+    clock = RoundClock(device, timing, cfg.eval_interval)
+
+    def store(rows, res, *row):
+        ring.push(*row)
+        if on_step is not None:
+            on_step(*row, res)
+
     for rnd in range(rounds):
-        sync()
-        t0 = time.perf_counter()
+        clock.start()
         mix.update_schedule((episodes + 1) / (rounds * n_arenas))  # update_schedule(ep, max_episodes)
-        if reset == "device":
-            obs, obs2 = (t.clone() for t in env.reset())
-        elif reset == "seeded" and hasattr(env, "reset_seeded"):
-            # the same episodes as below, drawn by the kernel: seeds and puck sides are reset_params' own
-            e = np.arange(rnd * n_arenas, (rnd + 1) * n_arenas, dtype=np.int64)
-            seeds = torch.arange(seed + 1 + rnd * n_arenas, seed + 1 + (rnd + 1) * n_arenas, device=env.device)
-            obs, obs2 = (t.clone() for t in env.reset_seeded(seeds, one_starting=(e % 2) == 1))
-        else:
-            # episode e = rnd * N + i + 1 is the train env's e-th reset: seed + e, puck side toggling per reset
-            p, _, _ = reset_params(n_arenas, seed + rnd * n_arenas + 1, mode, first_reset=rnd * n_arenas)
-            env.reset_params(p)
-            obs, obs2 = (t.clone() for t in env.observe())
+        obs, obs2 = reset_round(env, reset, mode, rnd, n_arenas, [seed])
         agent.reset_noise()
         ep_reward = torch.zeros(n_arenas, device=device)
         alive = torch.ones(n_arenas, dtype=torch.bool, device=device)  # episode_end="done": not yet done
@@ -720,31 +808,18 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
             res = env.step(act8, with_agent_two=True, policy2=policy2)
             o2, r, d = res.obs.clone(), res.reward.clone(), res.done.clone()
             round_steps += n_alive
-            if stop_at_done:  # only the transitions of episodes that were still running are stored
-                idx = torch.nonzero(alive).squeeze(1)
-                ring.push(obs[idx], a[idx], r[idx], o2[idx], d[idx])
-                if on_step is not None:
-                    on_step(obs[idx], a[idx], r[idx], o2[idx], d[idx], res)
-                mix.register_outcomes(d & alive, r)
-                ep_reward += torch.where(alive, r, torch.zeros_like(r))
-                alive &= d == 0
+            store_step(store, mix, stop_at_done, alive, ep_reward, res, obs, a, r, o2, d)
+            if stop_at_done:
                 n_alive = int(alive.sum())
                 if n_alive == 0:
                     break
-            else:
-                ring.push(obs, a, r, o2, d)
-                if on_step is not None:
-                    on_step(obs, a, r, o2, d, res)
-                mix.register_outcomes(d, r)
-                ep_reward += r
             obs, obs2 = o2, res.obs2.clone()
         episodes += n_arenas
         stats["env_steps"] += round_steps
         stats["mean_reward"].append(float(ep_reward.mean().item()))
         stats["opponents"].append(mix.end_round(agent.actor, episodes=n_arenas))
         stats["pool_size"].append(len(mix.pool) if mix.pool is not None else 0)
-        sync()
-        t1 = time.perf_counter()
+        clock.collected()
         if agent.total_steps > batch:  # _train_agent's guard (train.py:177-185)
             learner.run(updates)
             stats["updates"] += updates
@@ -752,12 +827,9 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
             stats["critic_loss"].append(cl)
             if al is not None:
                 stats["actor_loss"].append(al)
-        sync()
-        if timing:
-            stats["round_time"].append((t1 - t0, time.perf_counter() - t1))
-        if eval_fn is not None and episodes >= next_eval:
+        clock.updated([stats])
+        if eval_fn is not None and clock.eval_due(episodes):
             stats["evals"].append(eval_fn(agent, episodes))
-            next_eval = (episodes // cfg.eval_interval + 1) * cfg.eval_interval
         if log:
             log(rnd, stats)
     if own_env:

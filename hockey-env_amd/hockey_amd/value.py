@@ -23,7 +23,7 @@ import ctypes
 import torch
 
 from . import _native
-from .learner_hip import PACK_FLOATS, Net, ValueIO
+from .learner_hip import PACK_FLOATS, Net, ValueIO, check, lib, ptr, stream_ptr
 from .policy_bank import _hip_ready
 
 _LAYERS = ("fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias", "fc3.weight", "fc3.bias")
@@ -61,8 +61,7 @@ class _FlatNet:
     def net(self):
         if self.pack is None:
             self.pack = torch.zeros(PACK_FLOATS, dtype=torch.float32, device=self.flat.device)
-        return Net(*[ctypes.c_void_p(self.p[k].data_ptr()) for k in _LAYERS], ctypes.c_void_p(self.pack.data_ptr()),
-                   self.n_in, self.n_out)
+        return Net(*[ptr(self.p[k]) for k in _LAYERS], ptr(self.pack), self.n_in, self.n_out)
 
     def forward(self, x):
         p, lin = self.p, torch.nn.functional.linear
@@ -119,16 +118,11 @@ class ValueFn:
             dst.copy_(torch.as_tensor(critic[name]).detach().float())
         self._low, self._range = self.action_low.cpu().tolist(), self.action_range.cpu().tolist()
         if _hip_ready(self.device):
-            from .learner_hip import _check, lib
-
             nets = (Net * 3)(self.actor.net(), self.critics[0].net(), self.critics[1].net())
-            _check(lib().hkl_pack(nets, 3, None, self._stream()), "hkl_pack")
+            check(lib().hkl_pack(nets, 3, None, stream_ptr(self.device)), "hkl_pack")
         return self
 
     # ------------------------------------------------------------------ arguments
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _rows(self, t, name, cols, n=None):
         if not torch.is_tensor(t) or t.dim() != 2 or t.shape[1] < cols or t.dtype != torch.float32:
             got = f"{t.dtype} {tuple(t.shape)}" if torch.is_tensor(t) else type(t).__name__
@@ -151,8 +145,6 @@ class ValueFn:
     # ------------------------------------------------------------------ hip
     def _hip(self, obs, act, q1=False, q2=False, qmin=False, act_out=False):
         """One hkl_value call; returns the requested outputs (None for the others) as (q1, q2, qmin, act_out)."""
-        from .learner_hip import _check, lib
-
         if self.device.type != "cuda":
             raise _native.HockeyNativeError("ValueFn backend='hip' runs on the GPU only")
         if self.actor.pack is None:
@@ -173,7 +165,7 @@ class ValueFn:
             io.act_low[c], io.act_range[c] = self._low[c], self._range[c]
         io.q1, io.q2, io.qmin, io.act_out = (None if t is None else t.data_ptr() for t in out)
         io.act_out_ld = 4
-        _check(lib().hkl_value(ctypes.byref(io), self._stream()), "hkl_value")
+        check(lib().hkl_value(ctypes.byref(io), stream_ptr(self.device)), "hkl_value")
         return out
 
     # ------------------------------------------------------------------ torch (the reference path)
