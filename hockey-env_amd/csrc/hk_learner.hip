@@ -17,6 +17,7 @@
 //                 push with its sizes read on the device.
 //   act           acting: the actor forward of actor_step over a bank of policies, a different one per row, the rows
 //                 grouped by policy on the device.
+//   explore       act with TD3.act's exploration (annealed noise, random phase) as the acting tile's epilogue.
 //   value         twin-critic inference: Q_k(s, a), or V(s) = min Q_k(s, actor(s)) with the action kept in registers.
 //
 // The library's only translation unit: the kernels live in the headers below, included in the order of their
@@ -25,6 +26,7 @@
 #include "hkl_td3.h"    // Philox sampler, critic step, actor step, wgrad, adam, polyak, pack
 #include "hkl_per.h"    // prioritized replay
 #include "hkl_act.h"    // hkl_act / hkl_act_wide
+#include "hkl_explore.h"  // hkl_explore: hkl_act with the exploration epilogue
 #include "hkl_value.h"  // hkl_value
 
 using namespace hkl;
@@ -538,6 +540,47 @@ int hkl_act(const hkl_act_io *io, void *stream) {
   } else {
     hipLaunchKernelGGL(act_kernel, dim3(tiles), dim3(WG), 0, st, *io);
   }
+  return launched(who);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ C ABI: exploration acting
+extern "C" {
+
+int hkl_explore_io_size(void) { return (int)sizeof(hkl_explore_io); }
+int hkl_explore_member_size(void) { return (int)sizeof(hkl_explore_member); }
+
+int hkl_explore(const hkl_explore_io *io, const hkl_explore_member *members_host, void *stream) {
+  const char *who = "hkl_explore";
+  const auto bad = [](const hkl_explore_io &x) { return bad_act(x.act, HKL_ACT_MAX_POLICIES, true); };
+  if (const int rc = bad_io(who, io, bad)) return rc;
+  const hkl_act_io &act = io->act;
+  if (io->rows_per_member <= 0) return invalid(who, "rows_per_member <= 0");
+  if (act.n_rows == 0 || act.n_rows % io->rows_per_member) return invalid(who, "n_rows is no positive multiple of rows_per_member");
+  const int S = act.n_rows / io->rows_per_member;
+  if (const int rc = bad_group(who, members_host, io->members, S)) return rc;
+  if (!io->total || !io->calls || !io->count) return invalid(who, "null total / calls / count");
+  for (int m = 0; m < S; ++m) {
+    const hkl_explore_member &mem = members_host[m];
+    if (mem.anneal < HKL_ANNEAL_NONE || mem.anneal > HKL_ANNEAL_EXP) return bad_member(who, m, "anneal id out of range");
+    if (mem.noise < HKL_NOISE_NONE || mem.noise > HKL_NOISE_EXTERNAL) return bad_member(who, m, "noise id out of range");
+    if (mem.noise == HKL_NOISE_OU && !io->x) return bad_member(who, m, "null x with an OU member");
+    if (mem.noise == HKL_NOISE_EXTERNAL && !io->ext) return bad_member(who, m, "null ext with an external member");
+  }
+  const hipStream_t st = (hipStream_t)stream;
+  const unsigned tiles = blocks(act.n_rows, 64);
+  if (act.policy) {  // hkl_act's grouping launches as they are, behind a kernel in place of its memset
+    const unsigned rows = blocks(act.n_rows, 256);
+    hipLaunchKernelGGL(explore_zero_kernel, dim3(1), dim3(128), 0, st, act);
+    hipLaunchKernelGGL(act_hist_kernel, dim3(rows), dim3(256), 0, st, act);
+    hipLaunchKernelGGL(act_scan_kernel, dim3(1), dim3(64), 0, st, act);
+    hipLaunchKernelGGL(act_scatter_kernel, dim3(rows), dim3(256), 0, st, act);
+    hipLaunchKernelGGL(explore_kernel, dim3(tiles + (unsigned)act.n_policies), dim3(WG), 0, st, *io);
+  } else {
+    hipLaunchKernelGGL(explore_kernel, dim3(tiles), dim3(WG), 0, st, *io);
+  }
+  hipLaunchKernelGGL(explore_advance_kernel, dim3(1), dim3(HKL_GROUP_MAX), 0, st, *io, S);
   return launched(who);
 }
 

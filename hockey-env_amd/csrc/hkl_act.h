@@ -75,8 +75,17 @@ __global__ void __launch_bounds__(256) act_scatter_kernel(hkl_act_io io) {
 // One acting tile: policy k on the rows order[start .. start + min(cnt, 64)) (policy == NULL: the rows themselves).
 // IO is hkl_act_io or hkl_act_wide_io; act_kernel and act_wide_kernel differ only in how a workgroup finds (k, start,
 // cnt), so a row's four outputs are the same bits under either.  k, start and cnt are uniform over the workgroup.
-template <class IO>
-__device__ __forceinline__ void act_tile(const IO &io, int k, int start, int cnt, f4 *sfrag) {
+// Epi is what happens to the action a lane is about to store: epi(io, row, q, live, a), called by every lane (a spare
+// lane, live == false, must store nothing).  ActStore, the default, is the store itself; hkl_explore.h passes the
+// exploration epilogue.
+struct ActStore {
+  template <class IO>
+  __device__ __forceinline__ void operator()(const IO &io, int64_t row, int q, bool live, float a) const {
+    if (live) io.out[row * io.out_ld + io.out_col + q] = a;
+  }
+};
+template <class IO, class Epi = ActStore>
+__device__ __forceinline__ void act_tile(const IO &io, int k, int start, int cnt, f4 *sfrag, const Epi &epi = Epi()) {
   if (cnt <= 0) return;  // (never taken: a tile holds at least one row)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, j = lane & 15;
   // a partly filled workgroup: its spare lanes recompute the group's last row of this chunk and store nothing
@@ -95,15 +104,14 @@ __device__ __forceinline__ void act_tile(const IO &io, int k, int start, int cnt
   const f4 pre = gemm_out(an.fo(), h2, an.b2, an.b3, 4, lane, sfrag);
   // the sample's 4 lanes hold the same outputs: lane q stores component q
   const float a = tanh_fast(q == 0 ? pre[0] : q == 1 ? pre[1] : q == 2 ? pre[2] : pre[3]);
-  if (live) io.out[row * io.out_ld + io.out_col + q] = a;
+  epi(io, row, q, live, a);
 }
 
-__global__ void __launch_bounds__(WG, 1) act_kernel(hkl_act_io io) {
-  __shared__ f4 sfrag[2 * 16 * 64 + 64];  // two fragment buffers + the staged bias
-  // this workgroup's policy k and its rows [start, start + cnt) of the group, 64 per workgroup.  Everything up to
-  // the return depends on blockIdx and the arguments alone, so a surplus workgroup leaves as a whole before the
-  // first barrier.
-  int k = 0, start = 0, cnt = 0;
+// Workgroup blockIdx.x's policy k and its rows [start, start + cnt) of the group, 64 per workgroup; false for a
+// surplus workgroup.  The result depends on blockIdx and the arguments alone, so a surplus workgroup leaves as a
+// whole before the first barrier.
+__device__ __forceinline__ bool act_locate(const hkl_act_io &io, int &k, int &start, int &cnt) {
+  k = 0, start = 0, cnt = 0;
   if (io.policy) {
     int b = (int)blockIdx.x, lo = io.offsets[0];
     for (k = 0; k < io.n_policies; ++k) {
@@ -116,11 +124,18 @@ __global__ void __launch_bounds__(WG, 1) act_kernel(hkl_act_io io) {
       b -= tiles;
       lo = hi;
     }
-    if (k == io.n_policies) return;
+    if (k == io.n_policies) return false;
   } else {
     start = 64 * (int)blockIdx.x;
     cnt = io.n_rows - start;
   }
+  return true;
+}
+
+__global__ void __launch_bounds__(WG, 1) act_kernel(hkl_act_io io) {
+  __shared__ f4 sfrag[2 * 16 * 64 + 64];  // two fragment buffers + the staged bias
+  int k, start, cnt;
+  if (!act_locate(io, k, start, cnt)) return;
   act_tile(io, k, start, cnt, sfrag);
 }
 

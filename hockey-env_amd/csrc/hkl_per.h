@@ -1,5 +1,5 @@
 // hkl_per.h -- prioritized replay (rl/replay/prioritized_buffer.py) on per-block sums, for hk_learner.hip; uses
-// philox / sample_noise of hkl_td3.h.
+// philox (hkl_rng.h) and sample_noise of hkl_td3.h.
 //
 // PrioritizedRing.sample_indices is searchsorted(cumsum(p), u * sum(p), right) over all `cap` slots, with p the
 // sanitised weights (include/hockey_learner.h).  Here the ring is cut into blocks of PER_BLOCK = 64 x PER_SUB

@@ -2,6 +2,7 @@
 // Philox sampler, critic step, actor step, weight gradients, Adam, polyak and pack, each with its *_group twin.
 #pragma once
 #include "hkl_mlp.h"
+#include "hkl_rng.h"  // philox, box_muller
 
 namespace hkl {
 
@@ -10,21 +11,6 @@ namespace hkl {
 // counter = (sample, update, purpose)): uniform slots floor(u * size) with a 53-bit u (rl/replay/uniform_buffer.py's
 // (rand * size).astype(int)), and the target policy smoothing noise clamp(N(0, scale), -clip, clip) by Box-Muller
 // (learner.py:80-93).  The update counter lives in device memory (graph replays advance it): critic_step bumps it.
-struct P4 {
-  uint32_t x, y, z, w;
-};
-__device__ __forceinline__ P4 philox(uint64_t key, P4 c) {
-  uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-    c = P4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return c;
-}
 // sample e's replay slot of update `ctr` over `size` filled slots.  size <= 0 (an empty ring, or a fill word that is
 // out of contract) gives slot 0: out-of-contract device values are clamped, never addressed (as per_sample_body)
 __device__ __forceinline__ int64_t sample_slot(uint64_t seed, int64_t e, uint64_t ctr, int64_t size) {
@@ -37,19 +23,8 @@ __device__ __forceinline__ int64_t sample_slot(uint64_t seed, int64_t e, uint64_
 }
 // sample e's clipped target-smoothing noise of update `ctr`
 __device__ __forceinline__ f4 sample_noise(uint64_t seed, int64_t e, uint64_t ctr, float scale, float clip) {
-  const P4 r1 = philox(seed ^ 0x6E6F697365ull, P4{(uint32_t)e, (uint32_t)(e >> 32), (uint32_t)ctr, (uint32_t)(ctr >> 32)});
-  const uint32_t w[4] = {r1.x, r1.y, r1.z, r1.w};
   float z[4];
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    const float u1 = ((float)(w[2 * p] >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0, 1)
-    const float u2 = (float)(w[2 * p + 1] >> 8) * (1.0f / 16777216.0f);
-    const float rad = sqrtf(-2.0f * logf(u1));
-    float sn, cs;
-    sincosf(6.283185307179586f * u2, &sn, &cs);
-    z[2 * p] = rad * cs;
-    z[2 * p + 1] = rad * sn;
-  }
+  box_muller(philox_at(seed ^ 0x6E6F697365ull, e, ctr), z);
   f4 nz;
 #pragma unroll
   for (int c = 0; c < 4; ++c) nz[c] = fminf(fmaxf(z[c] * scale, -clip), clip);

@@ -1,5 +1,5 @@
 """ctypes binding of the fused fp32 MFMA TD3 learner (include/hockey_learner.h; the C ABI in csrc/hk_learner.hip, its
-kernels in csrc/hkl_mlp.h, hkl_td3.h, hkl_per.h, hkl_act.h and hkl_value.h).
+kernels in csrc/hkl_mlp.h, hkl_td3.h, hkl_per.h, hkl_act.h, hkl_explore.h and hkl_value.h).
 
 ``FusedLearner(agent, ring, batch)`` performs ``agent``'s learner updates (rl/td3/learner.py:55-218: clipped
 double-Q target with policy smoothing, weighted smooth-L1 critic loss, delayed actor update, Polyak averaging, Adam
@@ -17,7 +17,7 @@ the hkl_per_* kernels (per-block float64 sums; the slots come from the Philox st
 
 ``ActIO`` / ``hkl_act`` (actor inference over a bank of policies) and ``ActWideIO`` / ``hkl_act_wide`` (the same over up
 to 4 096 policies) are bound here and driven by ``hockey_amd.policy_bank.PolicyBank``; ``ValueIO`` / ``hkl_value`` (twin-critic inference) by
-``hockey_amd.value.ValueFn``.  The ``hkl_*_group`` forms (up to 64 independent learners per launch, each bit for bit
+``hockey_amd.value.ValueFn``; ``ExploreIO`` / ``hkl_explore`` (acting with exploration) by ``hockey_amd.explore.Explorer``.  The ``hkl_*_group`` forms (up to 64 independent learners per launch, each bit for bit
 its single call), ``hkl_per_*_group`` among them, are bound here and driven by
 ``hockey_amd.population.PopulationLearner`` and ``PopulationPrioritizedRing``.
 
@@ -122,6 +122,21 @@ class ActWideIO(ctypes.Structure):
                 ("out_col", ctypes.c_int32), ("order", vp), ("counts", vp), ("offsets", vp), ("tiles", vp)]
 
 
+class ExploreMember(ctypes.Structure):
+    """hkl_explore_member: one member's exploration parameters (hockey_amd.explore)."""
+    _fields_ = [("seed", ctypes.c_uint64), ("start_steps", ctypes.c_int64), ("max_total_steps", ctypes.c_int64),
+                ("init_scale", ctypes.c_double), ("min_scale", ctypes.c_double), ("anneal", ctypes.c_int32),
+                ("noise", ctypes.c_int32), ("theta", ctypes.c_float), ("dt", ctypes.c_float),
+                ("sqrt_dt", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
+class ExploreIO(ctypes.Structure):
+    """hkl_explore_io: hkl_act with the exploration epilogue (hockey_amd.explore)."""
+    _fields_ = [("act", ActIO), ("rows_per_member", ctypes.c_int32), ("members", vp), ("total", vp), ("calls", vp),
+                ("count", vp), ("x", vp), ("ext", vp), ("ext_ld", ctypes.c_int64), ("ext_cs", ctypes.c_int64),
+                ("z_out", vp), ("scale_out", vp)]
+
+
 def act_wide_max_tiles(n_rows, n_policies):
     """The bound on the non-empty 64-row tiles of hkl_act_wide: its ``tiles`` scratch holds 3 int32 per tile."""
     return min(n_rows, -(-n_rows // 64) + n_policies)
@@ -144,6 +159,9 @@ EXPORTS = ["hkl_last_error", "hkl_pack_floats", "hkl_pack", "hkl_critic_step", "
            "hkl_wgrad_pair_group", "hkl_adam_group", "hkl_pack_group", "hkl_per_sample_group",
            "hkl_per_weights_group", "hkl_per_update_group", "hkl_per_refresh_group", "hkl_per_push_group"]
 
+
+# include/hockey_explore.h (exploration acting), a header of its own beside hockey_learner.h's entry points above
+EXPLORE_EXPORTS = ["hkl_explore", "hkl_explore_io_size", "hkl_explore_member_size"]
 
 _lib = None
 
@@ -175,6 +193,7 @@ def lib():
         L.hkl_act.argtypes = [ctypes.POINTER(ActIO), vp]
         L.hkl_act_wide.argtypes = [ctypes.POINTER(ActWideIO), vp]
         L.hkl_value.argtypes = [ctypes.POINTER(ValueIO), vp]
+        L.hkl_explore.argtypes = [ctypes.POINTER(ExploreIO), ctypes.POINTER(ExploreMember), vp]
         # grouped forms: (host array, the same bytes on the device, ..., n_members, stream)
         L.hkl_sample_group.argtypes = [ctypes.POINTER(SampleIO), vp, ctypes.c_int, vp]
         L.hkl_critic_step_group.argtypes = [ctypes.POINTER(CriticIO), vp, ctypes.c_int, vp]
@@ -197,6 +216,9 @@ def lib():
             raise _native.HockeyNativeError("libhockey_learner.so hkl_act_wide_io differs from hockey_amd.learner_hip")
         if L.hkl_value_io_size() != ctypes.sizeof(ValueIO):
             raise _native.HockeyNativeError("libhockey_learner.so hkl_value_io differs from hockey_amd.learner_hip")
+        if (L.hkl_explore_io_size() != ctypes.sizeof(ExploreIO)
+                or L.hkl_explore_member_size() != ctypes.sizeof(ExploreMember)):
+            raise _native.HockeyNativeError("libhockey_learner.so hkl_explore_io differs from hockey_amd.learner_hip")
         _lib = L
     return _lib
 

@@ -246,6 +246,60 @@ class PolicyBank:
         (self._act_hip if backend == "hip" else self._act_torch)(obs, policy, out, out_col, _base_slot)
         return out
 
+    @torch.no_grad()
+    def explore(self, explorer, obs, out=None, out_col=0, count=None, ext=None):
+        """``act`` with exploration (hockey_amd.explore): row i runs slot ``explorer.policy[i]`` (slot 0 for a policy of
+        None) and ``explorer``'s law turns its action into the one to play, written to ``out[i, out_col : out_col +
+        4]``.  Under the explorer's backend "hip" this is ONE ``hkl_explore`` call (banks of up to 64 slots);
+        under "torch" the bank's torch forward followed by the law in numpy.  Returns ``out``."""
+        n, out_col, policy = explorer.N, int(out_col), explorer.policy
+        if obs.dim() != 2 or obs.shape != (n, obs.shape[1]) or obs.shape[1] < 18 or obs.dtype != torch.float32:
+            raise ValueError(f"obs must be float32 [{n}, >= 18], got {obs.dtype} {tuple(obs.shape)}")
+        if obs.device != self.device:
+            raise ValueError(f"obs is on {obs.device}, the bank on {self.device}")
+        if obs.stride(1) != 1 or obs.stride(0) < 18:
+            obs = obs.contiguous()
+        if out is None:
+            out = torch.zeros((n, out_col + 4), dtype=torch.float32, device=self.device)
+        if (out.dim() != 2 or out.shape[0] != n or out.dtype != torch.float32 or out.device != self.device or
+                out_col < 0 or out.shape[1] < out_col + 4 or (out.shape[1] > 1 and out.stride(1) != 1)
+                or out.stride(0) < out.shape[1]):
+            raise ValueError(f"out must be a float32 [n, >= out_col + 4] tensor with unit column stride on "
+                             f"{self.device}, got {out.dtype} {tuple(out.shape)}")
+        if policy is None and not self.occupied[0]:
+            raise ValueError("PolicyBank slot 0 is free")
+        if explorer.backend == "torch":
+            a = torch.zeros((n, 4), dtype=torch.float32, device=self.device)
+            self._act_torch(obs, policy, a, 0)
+            acting = None
+            if policy is not None:
+                occ = torch.tensor(self.occupied, device=self.device)
+                inside = (policy >= 0) & (policy < self.capacity)
+                acting = inside & occ[policy.clamp(0, self.capacity - 1).long()]
+            explorer._run_torch(a, acting, out, out_col, count, ext)
+            return out
+        if self.capacity > ACT_MAX_POLICIES:
+            raise _native.HockeyNativeError(f"hkl_explore takes banks of up to {ACT_MAX_POLICIES} slots")
+        if self.device.type != "cuda" or self._packs is None:
+            raise _native.HockeyNativeError("PolicyBank.explore backend='hip' needs a GPU and a packed slot")
+        io = ActIO()
+        io.n_rows = n
+        io.params, io.packs = self.params.data_ptr(), self._packs.data_ptr()
+        io.obs, io.obs_ld = obs.data_ptr(), obs.stride(0)
+        io.out, io.out_ld, io.out_col = out.data_ptr(), out.stride(0), out_col
+        io.n_policies = 1
+        if policy is not None:
+            io.n_policies = self.capacity
+            sc = self._scratch.get(n)
+            if sc is None:
+                sc = self._scratch[n] = tuple(torch.zeros(m, dtype=torch.int32, device=self.device)
+                                              for m in (n, ACT_MAX_POLICIES + 1, ACT_MAX_POLICIES + 1))
+            io.policy = policy.data_ptr()
+            io.order, io.counts, io.offsets = (t.data_ptr() for t in sc)
+        self._explore_obs = obs  # a contiguous copy stays alive until the next call
+        explorer._run_hip(io, count, ext)
+        return out
+
     def policy_fn(self, slot, backend="auto"):
         """``obs [n, 18] -> actions [n, 4]`` of one slot (``hockey_amd.evaluate.evaluate(policy=...)``)."""
         slot = self._slot(slot)

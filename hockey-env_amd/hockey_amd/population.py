@@ -21,7 +21,9 @@ What is and is not composition-independent: the LEARNER is -- its slots and targ
 Philox stream (seeded by the agent's seed), its arithmetic from the member's own grid slice.  COLLECTION is not: the
 exploration noise, the random-phase actions and the opponent draws come from torch generators shared by the
 population, and the step kernel's device draws are keyed by the global arena id, so a member's trajectory depends on
-its position in the population and on who else is in it.
+its position in the population and on who else is in it.  ``train_population(explore="device")`` takes the exploration
+out of that list: hockey_amd.explore keys each member's draws by its own seed, its arenas' indices inside the member and
+its own call counter.
 """
 import ctypes
 
@@ -360,7 +362,7 @@ def _check_members(members, per_ok=False, self_play_ok=False):
 
 def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode.NORMAL, episode_end="max_steps",
                      updates_per_round=None, eval_fn=None, on_step=None, env=None, replay_capacity=None, graphs=True,
-                     log=None, timing=False, self_play=None):
+                     log=None, timing=False, self_play=None, explore="torch"):
     """``hockey_amd.td3.train`` for S = len(members) agents side by side in one process.  ``members`` is a list of
     (TD3Config, seed) or (TD3Config, seed, resume_from); member j owns arenas [j n, (j + 1) n) of one VecHockeyEnv of
     S * n_arenas arenas (``env``: a ready batch of that many arenas, e.g. the kernel source's host build in the CPU
@@ -395,6 +397,14 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
     * on_step(member_of_row, arena_of_row, obs, action, reward, next_obs, done, step_result) sees every stored
       transition of a step, ragged over the members (test hook).
 
+    explore: "torch" (default) is the exploration described above.  "device" acts through one
+    ``hockey_amd.explore.Explorer`` over the S members: ONE ``hkl_explore`` call per step runs the bank, the members'
+    schedules, their noise and the random phase and writes player 1's columns of the step kernel's input; the members'
+    step counts live on the device (``episode_end="done"``: the running arenas are counted there) and reach
+    ``agent.total_steps`` / ``current_noise_scale`` at the end of a round.  Member j's exploration draws are then keyed by
+    its own seed, its arenas' indices inside the member and its own call counter: they do not depend on the population
+    (the opponent draws and the step kernel's draws still do).
+
     Collection randomness is shared: the exploration and opponent draws (bot or self-play, which bot, and with
     ``self_play`` which snapshot) come from torch generators of the whole population and the step kernel's device
     draws are keyed by the global arena id.  The self-play pools, their scores and their snapshot schedule are per
@@ -410,6 +420,8 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
     ms = _check_members(members, per_ok=dev.type == "cuda", self_play_ok=self_play is not None)
     if episode_end not in ("max_steps", "done"):
         raise ValueError("episode_end must be 'max_steps' or 'done'")
+    if explore not in ("torch", "device"):
+        raise ValueError("explore must be 'torch' or 'device'")
     S, n = len(ms), int(n_arenas)
     N = S * n
     c0 = ms[0][0]
@@ -454,6 +466,13 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
         rows = torch.cat([torch.arange(j * n, (j + 1) * n, device=dev) for j in js])
         gens[mname] = (make_noise(mname, rows.numel(), 4, 1.0, c0.max_steps, dev, ms[js[0]][1]), rows, js)
     start_t = torch.tensor([float(c.start_steps) for c, _, _ in ms], dtype=torch.float64, device=dev)
+    explorer = None
+    if explore == "device":
+        from .explore import Explorer, Member, sync_agents
+
+        # on a GPU the kernel, and an error without the library: no quiet fall-back to the numpy law
+        explorer = Explorer(bank, [Member.from_agent(ag) for ag in agents], n, policy=policy,
+                            backend="hip" if dev.type == "cuda" else "torch")
     act8 = torch.zeros((N, 8), device=dev)
     stats = [{"env_steps": 0, "updates": 0, "updates_per_round": updates, "batch": batch,
               "replay_ratio": updates * batch / (n * c0.max_steps), "replay_capacity": cap, "critic_loss": [],
@@ -477,51 +496,63 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
         clock.start()
         mix.update_schedule((episodes + 1) / (rounds * n))
         obs, obs2 = reset_round(env, "seeded", mode, rnd, n, [seed for _, seed, _ in ms])
-        for g, _, _ in gens.values():
-            g.reset()
+        if explorer is None:
+            for g, _, _ in gens.values():
+                g.reset()
+        else:
+            explorer.reset_noise()
+        count_t = None  # explore="device", episode_end="done": the members' running arenas, kept on the device
         ep_reward = torch.zeros(N, device=dev)
         alive = torch.ones(N, dtype=torch.bool, device=dev)
         n_alive = [n] * S  # per member: the arenas whose episode is still running
         round_steps = [0] * S
         for _ in range(c0.max_steps):
-            # ---- TD3.act per member: count, random phase, annealed scale (host scalars -> [S] tensors)
-            first = [ag.total_steps + 1 for ag in agents]
-            for ag, k in zip(agents, n_alive):
-                ag.total_steps += k
-            all_random = [ag.total_steps < ag.cfg.start_steps for ag in agents]
-            for ag, rnd_phase in zip(agents, all_random):
-                if not rnd_phase:
-                    ag.current_noise_scale = ag.noise_scale()
-            scale_t = torch.tensor([ag.current_noise_scale for ag in agents], dtype=torch.float32, device=dev)
-            first_t = torch.tensor(first, dtype=torch.float64, device=dev)
-            allr_t = torch.tensor(all_random, dtype=torch.bool, device=dev)
-            a = bank.act(obs, policy)
-            noise = torch.zeros((N, 4), device=dev)
-            for g, rows, js in gens.values():
-                if not all(all_random[j] for j in js):
-                    noise[rows] = g().float()
-            a = torch.clamp(a + noise * scale_t[member_of][:, None], -1, 1)
-            if any(f < ag.cfg.start_steps for f, ag in zip(first, agents)):
-                rnd_rows = allr_t[member_of] | ((local + first_t[member_of]) < start_t[member_of])
-                a = torch.where(rnd_rows[:, None], torch.rand((N, 4), device=dev) * 2 - 1, a)
+            if explorer is None:
+                # ---- TD3.act per member: count, random phase, annealed scale (host scalars -> [S] tensors)
+                first = [ag.total_steps + 1 for ag in agents]
+                for ag, k in zip(agents, n_alive):
+                    ag.total_steps += k
+                all_random = [ag.total_steps < ag.cfg.start_steps for ag in agents]
+                for ag, rnd_phase in zip(agents, all_random):
+                    if not rnd_phase:
+                        ag.current_noise_scale = ag.noise_scale()
+                scale_t = torch.tensor([ag.current_noise_scale for ag in agents], dtype=torch.float32, device=dev)
+                first_t = torch.tensor(first, dtype=torch.float64, device=dev)
+                allr_t = torch.tensor(all_random, dtype=torch.bool, device=dev)
+                a = bank.act(obs, policy)
+                noise = torch.zeros((N, 4), device=dev)
+                for g, rows, js in gens.values():
+                    if not all(all_random[j] for j in js):
+                        noise[rows] = g().float()
+                a = torch.clamp(a + noise * scale_t[member_of][:, None], -1, 1)
+                if any(f < ag.cfg.start_steps for f, ag in zip(first, agents)):
+                    rnd_rows = allr_t[member_of] | ((local + first_t[member_of]) < start_t[member_of])
+                    a = torch.where(rnd_rows[:, None], torch.rand((N, 4), device=dev) * 2 - 1, a)
+            else:  # one call: the actions land in act8[:, :4]
+                a = explorer.explore(obs, act8, 0, count=count_t)[:, :4]
             if self_play is None:
                 policy2, a2, _ = mix.select(obs2)
                 if a2 is not None:
                     act8[:, 4:] = a2
             else:  # the self-play arenas' actions go straight into act8[:, 4:8]
                 policy2, _, _ = mix.select(obs2, out=act8)
-            act8[:, :4] = a
+            if explorer is None:
+                act8[:, :4] = a
             res = env.step(act8, with_agent_two=True, policy2=policy2)
             o2, r, d = res.obs.clone(), res.reward.clone(), res.done.clone()
             for j in range(S):
                 round_steps[j] += n_alive[j]
             store_step(store, mix, stop_at_done, alive, ep_reward, res, obs, a, r, o2, d)
             if stop_at_done:
+                if explorer is not None:
+                    count_t = alive.view(S, n).sum(1, dtype=torch.int32)
                 n_alive = alive.view(S, n).sum(1).tolist()  # the step's one host sync, as train's
                 if not any(n_alive):
                     break
             obs, obs2 = o2, res.obs2.clone()
         episodes += n
+        if explorer is not None:
+            sync_agents(explorer, agents)
         if self_play is None:
             opp = [mix.end_round()] * S  # the population's counts: one mix over all arenas
         else:

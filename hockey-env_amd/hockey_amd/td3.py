@@ -698,7 +698,7 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
           curriculum=None, use_self_play=None, self_play_interval=None, pool_size=None, reset="seeded", log=None,
           replay_capacity=None, graphs=True, eval_fn=None, learner_batch=None, timing=False, replay_ratio=None,
           env=None, on_step=None, episode_end="max_steps", fused="auto", resume_from=None, per_sampler="torch",
-          self_play_sampling=None, mix=None):
+          self_play_sampling=None, mix=None, explore="torch"):
     """Batched TD3 training (rl/training/train.py TD3Trainer.train).  Each round runs ``max_steps`` steps of
     ``n_arenas`` parallel episodes (no break on done), stores every transition, then performs the learner
     updates of those episodes at the replay ratio: ``ratio * n_arenas * max_steps / B`` updates of batch B =
@@ -736,7 +736,13 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
     self_play_sampling: "step" (default, also None) draws one pool snapshot per step for all self-play arenas;
     "arena" draws one per arena and step, played through a PolicyBank in one call (hockey_amd.opponents); the
     round's ``stats["opponents"]`` entry then also lists the arena-steps per snapshot.  mix: a ready OpponentMix
-    for ``n_arenas`` on ``device`` to use instead of building one (a pool carried over from an earlier run)."""
+    for ``n_arenas`` on ``device`` to use instead of building one (a pool carried over from an earlier run).
+
+    explore: "torch" (default) acts through ``TD3.act``.  "device" acts through a ``hockey_amd.explore.Explorer`` on a
+    one-slot PolicyBank (refreshed after each round's updates): one ``hkl_explore`` call per step writes player 1's
+    action columns of the step kernel's input, the agent's step count and noise state live on the device, and
+    ``agent.total_steps`` / ``current_noise_scale`` are read back at the end of a round.  The law is ``TD3.act``'s; the
+    draws are Philox's, keyed by the agent's seed (hockey_amd.explore lists the batched differences)."""
     from .opponents import OpponentMix
     from .vec_env import VecHockeyEnv
 
@@ -745,6 +751,8 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
         raise ValueError("per_sampler must be 'torch' or 'device'")
     if reset not in ("seeded", "seeded_host", "device"):
         raise ValueError("reset must be 'seeded', 'seeded_host' or 'device'")
+    if explore not in ("torch", "device"):
+        raise ValueError("explore must be 'torch' or 'device'")
     curriculum = cfg.curriculum_name if curriculum is None else curriculum
     use_self_play = cfg.use_self_play if use_self_play is None else use_self_play
     self_play_interval = cfg.self_play_interval if self_play_interval is None else self_play_interval
@@ -781,6 +789,16 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
         raise ValueError("episode_end must be 'max_steps' or 'done'")
     stop_at_done = episode_end == "done"
     clock = RoundClock(device, timing, cfg.eval_interval)
+    explorer = None
+    if explore == "device":
+        from .explore import Explorer, Member, sync_agents
+        from .policy_bank import PolicyBank
+
+        bank = PolicyBank(1, agent.device)
+        bank.replace(0, agent.actor)
+        # on a GPU the kernel, and an error without the library: no quiet fall-back to the numpy law
+        explorer = Explorer(bank, [Member.from_agent(agent)], n_arenas,
+                            backend="hip" if agent.device.type == "cuda" else "torch")
 
     def store(rows, res, *row):
         ring.push(*row)
@@ -791,18 +809,26 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
         clock.start()
         mix.update_schedule((episodes + 1) / (rounds * n_arenas))  # update_schedule(ep, max_episodes)
         obs, obs2 = reset_round(env, reset, mode, rnd, n_arenas, [seed])
-        agent.reset_noise()
+        if explorer is None:
+            agent.reset_noise()
+        else:
+            explorer.reset_noise()
         ep_reward = torch.zeros(n_arenas, device=device)
         alive = torch.ones(n_arenas, dtype=torch.bool, device=device)  # episode_end="done": not yet done
         n_alive, round_steps = n_arenas, 0
+        count_t = None  # explore="device", episode_end="done": the running arenas, kept on the device
         for _ in range(cfg.max_steps):
-            a = agent.act(obs, count=n_alive)
+            if explorer is None:
+                a = agent.act(obs, count=n_alive)
+            else:  # lands in act8[:, :4] directly
+                a = explorer.explore(obs, act8, 0, count=count_t)[:, :4]
             if per_arena:  # the self-play arenas' actions land in act8[:, 4:8] directly
                 policy2, _, _ = mix.select(obs2, out=act8)
                 a2 = None
             else:
                 policy2, a2, _ = mix.select(obs2)
-            act8[:, :4] = a
+            if explorer is None:
+                act8[:, :4] = a
             if a2 is not None:
                 act8[:, 4:] = a2
             res = env.step(act8, with_agent_two=True, policy2=policy2)
@@ -810,11 +836,15 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
             round_steps += n_alive
             store_step(store, mix, stop_at_done, alive, ep_reward, res, obs, a, r, o2, d)
             if stop_at_done:
+                if explorer is not None:
+                    count_t = alive.sum(dtype=torch.int32).reshape(1)
                 n_alive = int(alive.sum())
                 if n_alive == 0:
                     break
             obs, obs2 = o2, res.obs2.clone()
         episodes += n_arenas
+        if explorer is not None:
+            sync_agents(explorer, [agent])
         stats["env_steps"] += round_steps
         stats["mean_reward"].append(float(ep_reward.mean().item()))
         stats["opponents"].append(mix.end_round(agent.actor, episodes=n_arenas))
@@ -827,6 +857,8 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
             stats["critic_loss"].append(cl)
             if al is not None:
                 stats["actor_loss"].append(al)
+            if explorer is not None:  # the actor changed: refresh the acting bank
+                bank.replace(0, agent.actor)
         clock.updated([stats])
         if eval_fn is not None and clock.eval_due(episodes):
             stats["evals"].append(eval_fn(agent, episodes))

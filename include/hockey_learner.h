@@ -299,6 +299,10 @@ typedef struct {
 int hkl_act_io_size(void);
 int hkl_act(const hkl_act_io *io, void *stream);
 
+/* ---- exploration acting: hkl_explore, hkl_act with TD3.act's exploration as the acting kernel's epilogue.  Its
+ * contract, structs and declaration fill a header of their own, which builds on hkl_act_io and HKL_GROUP_MAX above. */
+#include "hockey_explore.h"
+
 /* ---- actor inference over a wide bank (population self-play: one pool of snapshots per member) ----
  * hkl_act's contract with K = n_policies in [1, HKL_ACT_WIDE_MAX_POLICIES]: params, packs, obs, policy and out as
  * above, a row with policy[i] outside [0, K) is not written, no other float of out is, and a row's four actions are
