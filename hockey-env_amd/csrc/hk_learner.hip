@@ -18,6 +18,7 @@
 //   act           acting: the actor forward of actor_step over a bank of policies, a different one per row, the rows
 //                 grouped by policy on the device.
 //   explore       act with TD3.act's exploration (annealed noise, random phase) as the acting tile's epilogue.
+//   collect       what a training step does around the step kernel: the opponent draw and the replay store.
 //   value         twin-critic inference: Q_k(s, a), or V(s) = min Q_k(s, actor(s)) with the action kept in registers.
 //
 // The library's only translation unit: the kernels live in the headers below, included in the order of their
@@ -27,6 +28,7 @@
 #include "hkl_per.h"    // prioritized replay
 #include "hkl_act.h"    // hkl_act / hkl_act_wide
 #include "hkl_explore.h"  // hkl_explore: hkl_act with the exploration epilogue
+#include "hkl_collect.h"  // hkl_opp_draw, hkl_collect
 #include "hkl_value.h"  // hkl_value
 
 using namespace hkl;
@@ -581,6 +583,70 @@ int hkl_explore(const hkl_explore_io *io, const hkl_explore_member *members_host
     hipLaunchKernelGGL(explore_kernel, dim3(tiles), dim3(WG), 0, st, *io);
   }
   hipLaunchKernelGGL(explore_advance_kernel, dim3(1), dim3(HKL_GROUP_MAX), 0, st, *io, S);
+  return launched(who);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ C ABI: collection
+// the member layout both calls share: what is wrong with (n_rows, rows_per_member, pmax), or nullptr
+static const char *bad_layout(int32_t n_rows, int32_t n, int32_t pmax) {
+  if (n <= 0) return "rows_per_member <= 0";
+  if (n_rows <= 0 || n_rows % n) return "n_rows is no positive multiple of rows_per_member";
+  if (n_rows / n > HKL_GROUP_MAX) return "n_members (n_rows / rows_per_member) outside [1, HKL_GROUP_MAX]";
+  return pmax < 1 ? "pmax < 1" : nullptr;
+}
+static const char *bad_opp_draw(const hkl_opp_draw_io &io) {
+  if (const char *w = bad_layout(io.n_rows, io.rows_per_member, io.pmax)) return w;
+  if (!io.seeds || !io.calls || !io.probs || !io.len || !io.scores || !io.slots)
+    return "null seeds / calls / probs / len / scores / slots";
+  return (!io.policy2 || !io.policy || !io.snap || !io.counts || !io.snap_counts)
+             ? "null policy2 / policy / snap / counts / snap_counts" : nullptr;
+}
+static const char *bad_collect(const hkl_collect_io &io) {
+  if (const char *w = bad_layout(io.n_rows, io.rows_per_member, io.pmax)) return w;
+  if (io.cap < 1 || io.rows_per_member > io.cap) return "cap < 1 or rows_per_member > cap";
+  if (io.act_ld < 4) return "act_ld < 4";
+  if (!io.obs || !io.act || !io.obs_next || !io.reward || !io.done) return "null obs / act / obs_next / reward / done";
+  if (!io.s || !io.a || !io.r || !io.s2 || !io.d || !io.pos || !io.size) return "null ring column / pos / size";
+  if (!io.ep_reward || !io.push_pos || !io.push_n || !io.steps || !io.scratch)
+    return "null ep_reward / push_pos / push_n / steps / scratch";
+  if (io.snap && !io.tally) return "snap without tally";
+  if (io.alive && !io.count) return "alive without count";
+  return (io.keep_obs2 && !io.obs2_next) ? "keep_obs2 without obs2_next" : nullptr;
+}
+
+extern "C" {
+
+int hkl_opp_draw_io_size(void) { return (int)sizeof(hkl_opp_draw_io); }
+int hkl_collect_io_size(void) { return (int)sizeof(hkl_collect_io); }
+int64_t hkl_collect_scratch_ints(int32_t n_rows, int32_t rows_per_member) {
+  if (rows_per_member <= 0 || n_rows <= 0) return 0;
+  return HKL_GROUP_MAX + 3 * (int64_t)(n_rows / rows_per_member) * collect_nb(rows_per_member);
+}
+
+int hkl_opp_draw(const hkl_opp_draw_io *io, void *stream) {
+  const char *who = "hkl_opp_draw";
+  if (const int rc = bad_io(who, io, bad_opp_draw)) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  const int S = io->n_rows / io->rows_per_member;
+  hipLaunchKernelGGL(opp_draw_kernel, dim3(blocks(io->rows_per_member, CWG), S), dim3(CWG), 0, st, *io);
+  hipLaunchKernelGGL(opp_advance_kernel, dim3(1), dim3(HKL_GROUP_MAX), 0, st, *io, S);
+  return launched(who);
+}
+
+int hkl_collect(const hkl_collect_io *io, void *stream) {
+  const char *who = "hkl_collect";
+  if (const int rc = bad_io(who, io, bad_collect)) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(blocks(io->rows_per_member, CWG), io->n_rows / io->rows_per_member);
+  if (io->alive) {
+    hipLaunchKernelGGL(collect_count_kernel, grid, dim3(CWG), 0, st, *io);
+    hipLaunchKernelGGL(collect_scan_kernel, dim3(grid.y), dim3(CWG), 0, st, *io);
+    hipLaunchKernelGGL(collect_store_kernel<true>, grid, dim3(CWG), 0, st, *io);
+  } else {
+    hipLaunchKernelGGL(collect_store_kernel<false>, grid, dim3(CWG), 0, st, *io);
+  }
   return launched(who);
 }
 

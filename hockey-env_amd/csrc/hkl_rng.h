@@ -1,5 +1,5 @@
 // hkl_rng.h -- the learner library's counter-based draws, shared by the sampler (hkl_td3.h, hkl_per.h) and the
-// exploration epilogue (hkl_explore.h): Philox4x32-10 and the Box-Muller normals of one Philox block.
+// exploration epilogue (hkl_explore.h) and the opponent draw (hkl_collect.h): Philox4x32-10 and the Box-Muller normals of one Philox block.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -39,6 +39,10 @@ __device__ __forceinline__ float fmul_rn(float a, float b) {
 __device__ __forceinline__ float fadd_rn(float a, float b) {
 #pragma clang fp contract(off)
   return a + b;
+}
+__device__ __forceinline__ double dmul_rn(double a, double b) {
+#pragma clang fp contract(off)
+  return a * b;
 }
 
 // four N(0, 1) draws of one block: Box-Muller on the word pairs (x, y) and (z, w) -- u1 = ((w >> 8) + 0.5) 2^-24 in

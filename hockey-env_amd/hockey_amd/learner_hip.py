@@ -17,7 +17,9 @@ the hkl_per_* kernels (per-block float64 sums; the slots come from the Philox st
 
 ``ActIO`` / ``hkl_act`` (actor inference over a bank of policies) and ``ActWideIO`` / ``hkl_act_wide`` (the same over up
 to 4 096 policies) are bound here and driven by ``hockey_amd.policy_bank.PolicyBank``; ``ValueIO`` / ``hkl_value`` (twin-critic inference) by
-``hockey_amd.value.ValueFn``; ``ExploreIO`` / ``hkl_explore`` (acting with exploration) by ``hockey_amd.explore.Explorer``.  The ``hkl_*_group`` forms (up to 64 independent learners per launch, each bit for bit
+``hockey_amd.value.ValueFn``; ``ExploreIO`` / ``hkl_explore`` (acting with exploration) by ``hockey_amd.explore.Explorer``; ``OppDrawIO`` /
+``hkl_opp_draw`` and ``CollectIO`` / ``hkl_collect`` (the opponent draw and the replay store of a collection step) by
+``hockey_amd.collect.Collector``.  The ``hkl_*_group`` forms (up to 64 independent learners per launch, each bit for bit
 its single call), ``hkl_per_*_group`` among them, are bound here and driven by
 ``hockey_amd.population.PopulationLearner`` and ``PopulationPrioritizedRing``.
 
@@ -137,6 +139,24 @@ class ExploreIO(ctypes.Structure):
                 ("z_out", vp), ("scale_out", vp)]
 
 
+class OppDrawIO(ctypes.Structure):
+    """hkl_opp_draw_io: player 2's opponent draw, one lane per arena (hockey_amd.collect)."""
+    _fields_ = [("n_rows", ctypes.c_int32), ("rows_per_member", ctypes.c_int32), ("pmax", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("seeds", vp), ("calls", vp), ("probs", vp), ("len", vp), ("scores", vp),
+                ("slots", vp), ("alive", vp), ("policy2", vp), ("policy", vp), ("snap", vp), ("opp_inc", vp),
+                ("counts", vp), ("snap_counts", vp)]
+
+
+class CollectIO(ctypes.Structure):
+    """hkl_collect_io: the replay store and the step's bookkeeping (hockey_amd.collect)."""
+    _fields_ = [("n_rows", ctypes.c_int32), ("rows_per_member", ctypes.c_int32), ("pmax", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("obs", vp), ("act", vp), ("act_ld", ctypes.c_int64), ("obs_next", vp),
+                ("obs2_next", vp), ("reward", vp), ("done", vp), ("snap", vp), ("alive", vp), ("s", vp), ("a", vp),
+                ("r", vp), ("s2", vp), ("d", vp), ("cap", ctypes.c_int64), ("pos", vp), ("size", vp),
+                ("ep_reward", vp), ("tally", vp), ("push_pos", vp), ("push_n", vp), ("count", vp), ("steps", vp),
+                ("live", vp), ("keep_obs", vp), ("keep_obs2", vp), ("scratch", vp)]
+
+
 def act_wide_max_tiles(n_rows, n_policies):
     """The bound on the non-empty 64-row tiles of hkl_act_wide: its ``tiles`` scratch holds 3 int32 per tile."""
     return min(n_rows, -(-n_rows // 64) + n_policies)
@@ -162,6 +182,10 @@ EXPORTS = ["hkl_last_error", "hkl_pack_floats", "hkl_pack", "hkl_critic_step", "
 
 # include/hockey_explore.h (exploration acting), a header of its own beside hockey_learner.h's entry points above
 EXPLORE_EXPORTS = ["hkl_explore", "hkl_explore_io_size", "hkl_explore_member_size"]
+
+# include/hockey_collect.h (the opponent draw and the replay store), likewise
+COLLECT_EXPORTS = ["hkl_opp_draw", "hkl_opp_draw_io_size", "hkl_collect", "hkl_collect_io_size",
+                   "hkl_collect_scratch_ints"]
 
 _lib = None
 
@@ -194,6 +218,10 @@ def lib():
         L.hkl_act_wide.argtypes = [ctypes.POINTER(ActWideIO), vp]
         L.hkl_value.argtypes = [ctypes.POINTER(ValueIO), vp]
         L.hkl_explore.argtypes = [ctypes.POINTER(ExploreIO), ctypes.POINTER(ExploreMember), vp]
+        L.hkl_opp_draw.argtypes = [ctypes.POINTER(OppDrawIO), vp]
+        L.hkl_collect.argtypes = [ctypes.POINTER(CollectIO), vp]
+        L.hkl_collect_scratch_ints.argtypes = [ctypes.c_int32, ctypes.c_int32]
+        L.hkl_collect_scratch_ints.restype = ctypes.c_int64
         # grouped forms: (host array, the same bytes on the device, ..., n_members, stream)
         L.hkl_sample_group.argtypes = [ctypes.POINTER(SampleIO), vp, ctypes.c_int, vp]
         L.hkl_critic_step_group.argtypes = [ctypes.POINTER(CriticIO), vp, ctypes.c_int, vp]
@@ -219,6 +247,9 @@ def lib():
         if (L.hkl_explore_io_size() != ctypes.sizeof(ExploreIO)
                 or L.hkl_explore_member_size() != ctypes.sizeof(ExploreMember)):
             raise _native.HockeyNativeError("libhockey_learner.so hkl_explore_io differs from hockey_amd.learner_hip")
+        if (L.hkl_opp_draw_io_size() != ctypes.sizeof(OppDrawIO)
+                or L.hkl_collect_io_size() != ctypes.sizeof(CollectIO)):
+            raise _native.HockeyNativeError("libhockey_learner.so hkl_collect_io differs from hockey_amd.learner_hip")
         _lib = L
     return _lib
 

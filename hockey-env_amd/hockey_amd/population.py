@@ -23,9 +23,12 @@ exploration noise, the random-phase actions and the opponent draws come from tor
 population, and the step kernel's device draws are keyed by the global arena id, so a member's trajectory depends on
 its position in the population and on who else is in it.  ``train_population(explore="device")`` takes the exploration
 out of that list: hockey_amd.explore keys each member's draws by its own seed, its arenas' indices inside the member and
-its own call counter.
+its own call counter.  ``train_population(collect="device")`` takes the rest: hockey_amd.collect keys the opponent
+draws and the bots' phases the same way and supplies the step kernel's draws, so that member j's whole run -- its
+trajectories, replay ring and weights -- is the same bits alone and inside a population of 64.
 """
 import ctypes
+import dataclasses
 
 import torch
 
@@ -362,7 +365,7 @@ def _check_members(members, per_ok=False, self_play_ok=False):
 
 def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode.NORMAL, episode_end="max_steps",
                      updates_per_round=None, eval_fn=None, on_step=None, env=None, replay_capacity=None, graphs=True,
-                     log=None, timing=False, self_play=None, explore="torch"):
+                     log=None, timing=False, self_play=None, explore="torch", collect="torch", poll_every=16):
     """``hockey_amd.td3.train`` for S = len(members) agents side by side in one process.  ``members`` is a list of
     (TD3Config, seed) or (TD3Config, seed, resume_from); member j owns arenas [j n, (j + 1) n) of one VecHockeyEnv of
     S * n_arenas arenas (``env``: a ready batch of that many arenas, e.g. the kernel source's host build in the CPU
@@ -405,7 +408,18 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
     its own seed, its arenas' indices inside the member and its own call counter: they do not depend on the population
     (the opponent draws and the step kernel's draws still do).
 
-    Collection randomness is shared: the exploration and opponent draws (bot or self-play, which bot, and with
+    collect: "torch" (default) is the collection described above.  "device" (needs explore="device"; self_play None or
+    "arena"; no on_step) runs every step through one ``hockey_amd.collect.Collector``: after ``hkl_explore``, one
+    ``hkl_opp_draw`` (bot or self-play, which bot, which snapshot, the bots' phase increments, the opponent counts), one
+    ``PolicyBank.act`` for the self-play arenas, the step kernel and one ``hkl_collect`` (the ragged replay store, write
+    positions, episode rewards, outcome tally, survivors), then ``hkl_per_push_group`` for prioritized members -- no torch
+    op on an [N]-row tensor in between and nothing read back but, under episode_end="done", the survivors' count every
+    ``poll_every`` steps (the results do not depend on it).  Player 2 is then always a ``PopulationOpponentMix`` (without
+    ``self_play`` one whose members keep no pools) and ``stats[j]["opponents"]`` member j's own counts, taken over its
+    running arenas.  Every draw of collection is then keyed by the member's seed: member j's trajectories, ring and
+    weights are the same bits alone and in any population (hockey_amd.collect lists the batched differences).
+
+    Collection randomness is shared under collect="torch": the exploration and opponent draws (bot or self-play, which bot, and with
     ``self_play`` which snapshot) come from torch generators of the whole population and the step kernel's device
     draws are keyed by the global arena id.  The self-play pools, their scores and their snapshot schedule are per
     member.  A member's trajectory therefore
@@ -422,6 +436,17 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
         raise ValueError("episode_end must be 'max_steps' or 'done'")
     if explore not in ("torch", "device"):
         raise ValueError("explore must be 'torch' or 'device'")
+    if collect not in ("torch", "device"):
+        raise ValueError("collect must be 'torch' or 'device'")
+    if collect == "device":
+        if explore != "device":
+            raise ValueError("collect='device' runs behind hkl_explore: it needs explore='device'")
+        if self_play == "step":
+            raise ValueError("collect='device' draws a snapshot per arena and step: self_play='step' sampling is not "
+                             "supported on the device, pass self_play='arena'")
+        if on_step is not None:
+            raise ValueError("collect='device' stores the transitions on the device without materialising a step's "
+                             "rows: on_step is not supported")
     S, n = len(ms), int(n_arenas)
     N = S * n
     c0 = ms[0][0]
@@ -438,7 +463,10 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
 
         env = VecHockeyEnv(N, mode=mode, device=dev, policies=("external", "external"), auto_reset=False,
                            seed=ms[0][1])
-    if self_play is None:
+    if collect == "device" and self_play is None:  # the Collector's mix, with no member keeping a pool
+        mix = PopulationOpponentMix([dataclasses.replace(c, use_self_play=False) for c, _, _ in ms],
+                                    [s for _, s, _ in ms], n, dev, sampling="arena")
+    elif self_play is None:
         mix = OpponentMix(N, c0.curriculum_name, False, c0.self_play_interval, c0.self_play_pool_size, dev, ms[0][1])
     else:
         mix = PopulationOpponentMix([c for c, _, _ in ms], [s for _, s, _ in ms], n, dev, sampling=self_play)
@@ -473,6 +501,13 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
         # on a GPU the kernel, and an error without the library: no quiet fall-back to the numpy law
         explorer = Explorer(bank, [Member.from_agent(ag) for ag in agents], n, policy=policy,
                             backend="hip" if dev.type == "cuda" else "torch")
+    collector = None
+    if collect == "device":
+        from .collect import Collector
+
+        collector = Collector(env, bank, mix, ring, explorer, [s for _, s, _ in ms], n,
+                              backend="hip" if dev.type == "cuda" else "torch", episode_end=episode_end,
+                              poll_every=poll_every)
     act8 = torch.zeros((N, 8), device=dev)
     stats = [{"env_steps": 0, "updates": 0, "updates_per_round": updates, "batch": batch,
               "replay_ratio": updates * batch / (n * c0.max_steps), "replay_capacity": cap, "critic_loss": [],
@@ -506,7 +541,10 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
         alive = torch.ones(N, dtype=torch.bool, device=dev)
         n_alive = [n] * S  # per member: the arenas whose episode is still running
         round_steps = [0] * S
-        for _ in range(c0.max_steps):
+        if collector is not None:  # the whole round on the device; the loop below is collect="torch"'s
+            collector.begin_round(obs, obs2, c0.max_steps)
+            collector.run_round()
+        for _ in range(c0.max_steps if collector is None else 0):
             if explorer is None:
                 # ---- TD3.act per member: count, random phase, annealed scale (host scalars -> [S] tensors)
                 first = [ag.total_steps + 1 for ag in agents]
@@ -553,7 +591,9 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
         episodes += n
         if explorer is not None:
             sync_agents(explorer, agents)
-        if self_play is None:
+        if collector is not None:  # per member; the snapshots precede the updates
+            round_steps, ep_reward, opp = collector.end_round([ag.actor for ag in agents], n)
+        elif self_play is None:
             opp = [mix.end_round()] * S  # the population's counts: one mix over all arenas
         else:
             opp = mix.end_round([ag.actor for ag in agents], n)  # per member; snapshots precede the updates

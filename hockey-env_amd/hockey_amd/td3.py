@@ -698,7 +698,7 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
           curriculum=None, use_self_play=None, self_play_interval=None, pool_size=None, reset="seeded", log=None,
           replay_capacity=None, graphs=True, eval_fn=None, learner_batch=None, timing=False, replay_ratio=None,
           env=None, on_step=None, episode_end="max_steps", fused="auto", resume_from=None, per_sampler="torch",
-          self_play_sampling=None, mix=None, explore="torch"):
+          self_play_sampling=None, mix=None, explore="torch", collect="torch", poll_every=16):
     """Batched TD3 training (rl/training/train.py TD3Trainer.train).  Each round runs ``max_steps`` steps of
     ``n_arenas`` parallel episodes (no break on done), stores every transition, then performs the learner
     updates of those episodes at the replay ratio: ``ratio * n_arenas * max_steps / B`` updates of batch B =
@@ -742,7 +742,16 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
     one-slot PolicyBank (refreshed after each round's updates): one ``hkl_explore`` call per step writes player 1's
     action columns of the step kernel's input, the agent's step count and noise state live on the device, and
     ``agent.total_steps`` / ``current_noise_scale`` are read back at the end of a round.  The law is ``TD3.act``'s; the
-    draws are Philox's, keyed by the agent's seed (hockey_amd.explore lists the batched differences)."""
+    draws are Philox's, keyed by the agent's seed (hockey_amd.explore lists the batched differences).
+
+    collect: "torch" (default) is the loop described above.  "device" (needs explore="device") runs every step through a
+    one-member ``hockey_amd.collect.Collector``: ``hkl_explore``, ``hkl_opp_draw``, one ``PolicyBank.act`` for the
+    self-play arenas, the step kernel and ``hkl_collect``, with nothing read back per step (episode_end="done": the
+    survivors' count every ``poll_every`` steps; the results do not depend on it).  The ring is then a one-member
+    ``PopulationRing`` (prioritized replay: a ``PopulationPrioritizedRing``, which needs per_sampler="device" and the
+    fused learner) and the mix a one-member ``PopulationOpponentMix`` with a snapshot drawn per arena and step, so
+    ``self_play_sampling="step"``, a ready ``mix`` and ``on_step`` raise ValueError.  hockey_amd.collect lists the
+    batched differences from collect="torch"."""
     from .opponents import OpponentMix
     from .vec_env import VecHockeyEnv
 
@@ -753,6 +762,23 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
         raise ValueError("reset must be 'seeded', 'seeded_host' or 'device'")
     if explore not in ("torch", "device"):
         raise ValueError("explore must be 'torch' or 'device'")
+    if collect not in ("torch", "device"):
+        raise ValueError("collect must be 'torch' or 'device'")
+    if collect == "device":
+        if explore != "device":
+            raise ValueError("collect='device' runs behind hkl_explore: it needs explore='device'")
+        if self_play_sampling == "step":
+            raise ValueError("collect='device' draws a snapshot per arena and step: self_play_sampling='step' is not "
+                             "supported on the device")
+        if mix is not None:
+            raise ValueError("collect='device' builds its own one-member PopulationOpponentMix: a ready mix is not "
+                             "supported")
+        if on_step is not None:
+            raise ValueError("collect='device' stores the transitions on the device without materialising a step's "
+                             "rows: on_step is not supported")
+        if cfg.prioritized_replay and per_sampler != "device":
+            raise ValueError("collect='device' pushes priorities through hkl_per_push_group: prioritized replay needs "
+                             "per_sampler='device'")
     curriculum = cfg.curriculum_name if curriculum is None else curriculum
     use_self_play = cfg.use_self_play if use_self_play is None else use_self_play
     self_play_interval = cfg.self_play_interval if self_play_interval is None else self_play_interval
@@ -765,7 +791,15 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
     if own_env:
         env = VecHockeyEnv(n_arenas, mode=mode, device=device, policies=("external", "external"), auto_reset=False,
                            seed=seed)
-    if mix is None:
+    if collect == "device":
+        from dataclasses import replace
+
+        from .opponents import PopulationOpponentMix
+
+        mix = PopulationOpponentMix([replace(cfg, use_self_play=bool(use_self_play), self_play_pool_size=pool_size,
+                                             self_play_interval=self_play_interval)], [seed], n_arenas, device,
+                                    sampling="arena", curriculum=curriculum)
+    elif mix is None:
         mix = OpponentMix(n_arenas, curriculum, use_self_play, self_play_interval, pool_size, device, seed,
                           sampling=self_play_sampling or "step")
     elif self_play_sampling is not None and mix.sampling != self_play_sampling:
@@ -773,10 +807,20 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
     per_arena = mix.sampling == "arena"
     cap = replay_capacity or max(cfg.buffer_size, n_arenas * cfg.max_steps)
     per_ring = DevicePrioritizedRing if per_sampler == "device" else PrioritizedRing
-    ring = (per_ring(cap, device=device, beta=cfg.beta) if cfg.prioritized_replay
-            else ReplayRing(cap, device=device))
+    pop_ring = None
+    if collect == "device":  # the Collector's store: a population ring of one member
+        from .population import PopulationPrioritizedRing, PopulationRing
+
+        pop_ring = (PopulationPrioritizedRing(1, cap, beta=cfg.beta, device=device) if cfg.prioritized_replay
+                    else PopulationRing(1, cap, device=device))
+        ring = pop_ring.member(0)
+    else:
+        ring = (per_ring(cap, device=device, beta=cfg.beta) if cfg.prioritized_replay
+                else ReplayRing(cap, device=device))
     batch = int(learner_batch or cfg.batch_size)
     learner = Learner(agent, ring, batch, graphs=graphs, fused=fused)
+    if pop_ring is not None and cfg.prioritized_replay and learner.fused is None:
+        raise ValueError("collect='device' with prioritized replay samples through the fused learner only")
     updates = updates_per_round if updates_per_round is not None else \
         updates_for(cfg, n_arenas, cfg.max_steps, batch, replay_ratio)
     act8 = torch.zeros((n_arenas, 8), device=device)
@@ -800,6 +844,14 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
         explorer = Explorer(bank, [Member.from_agent(agent)], n_arenas,
                             backend="hip" if agent.device.type == "cuda" else "torch")
 
+    collector = None
+    if collect == "device":
+        from .collect import Collector
+
+        collector = Collector(env, bank, mix, pop_ring, explorer, [seed], n_arenas,
+                              backend="hip" if agent.device.type == "cuda" else "torch", episode_end=episode_end,
+                              poll_every=poll_every)
+
     def store(rows, res, *row):
         ring.push(*row)
         if on_step is not None:
@@ -817,7 +869,10 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
         alive = torch.ones(n_arenas, dtype=torch.bool, device=device)  # episode_end="done": not yet done
         n_alive, round_steps = n_arenas, 0
         count_t = None  # explore="device", episode_end="done": the running arenas, kept on the device
-        for _ in range(cfg.max_steps):
+        if collector is not None:  # the whole round on the device; the loop below is collect="torch"'s
+            collector.begin_round(obs, obs2, cfg.max_steps)
+            collector.run_round()
+        for _ in range(cfg.max_steps if collector is None else 0):
             if explorer is None:
                 a = agent.act(obs, count=n_alive)
             else:  # lands in act8[:, :4] directly
@@ -845,10 +900,15 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
         episodes += n_arenas
         if explorer is not None:
             sync_agents(explorer, [agent])
+        if collector is not None:
+            (round_steps,), ep_reward, (opp,) = collector.end_round([agent.actor], n_arenas)
+        else:
+            opp = mix.end_round(agent.actor, episodes=n_arenas)
         stats["env_steps"] += round_steps
         stats["mean_reward"].append(float(ep_reward.mean().item()))
-        stats["opponents"].append(mix.end_round(agent.actor, episodes=n_arenas))
-        stats["pool_size"].append(len(mix.pool) if mix.pool is not None else 0)
+        stats["opponents"].append(opp)
+        stats["pool_size"].append(mix.pool_sizes()[0] if collector is not None else
+                                  len(mix.pool) if mix.pool is not None else 0)
         clock.collected()
         if agent.total_steps > batch:  # _train_agent's guard (train.py:177-185)
             learner.run(updates)

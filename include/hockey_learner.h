@@ -303,6 +303,10 @@ int hkl_act(const hkl_act_io *io, void *stream);
  * contract, structs and declaration fill a header of their own, which builds on hkl_act_io and HKL_GROUP_MAX above. */
 #include "hockey_explore.h"
 
+/* ---- collection on the device: the opponent draw before the step and the replay store after it, in a header of
+ * their own beside the exploration's. */
+#include "hockey_collect.h"
+
 /* ---- actor inference over a wide bank (population self-play: one pool of snapshots per member) ----
  * hkl_act's contract with K = n_policies in [1, HKL_ACT_WIDE_MAX_POLICIES]: params, packs, obs, policy and out as
  * above, a row with policy[i] outside [0, K) is not written, no other float of out is, and a row's four actions are

@@ -125,6 +125,10 @@ def main():
     ap.add_argument("--explore", choices=["torch", "device"], default="torch",
                     help="--population: player 1's exploration acting, train_population(explore=...); 'device' is one "
                          "hkl_explore call per step with each member's draws keyed by its own seed")
+    ap.add_argument("--collect", choices=["torch", "device"], default="torch",
+                    help="--population: the rest of a collection step, train_population(collect=...); 'device' (needs "
+                         "--explore device) is hkl_opp_draw + hkl_collect around the step kernel, every draw keyed by "
+                         "the member's own seed: a member's run no longer depends on the population")
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "noise_study"))
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
@@ -147,12 +151,13 @@ def main():
         self_play = "arena" if any(r.cfg.use_self_play for r in runs) else None
         _, stats = train_population(members, n_arenas=n, rounds=rounds, device="cuda:0", episode_end="done",
                                     eval_fn=lambda ag, ep: by_member[key(ag.cfg, ag.seed)].eval_fn(ag, ep),
-                                    self_play=self_play, explore=args.explore)
+                                    self_play=self_play, explore=args.explore, collect=args.collect)
         torch.cuda.synchronize()
         for r, st in zip(runs, stats):
-            r.out["population"] = len(runs)  # collection randomness is shared by the population's members
+            r.out["population"] = len(runs)  # collect="torch": the members share collection randomness
             r.out["self_play_sampling"] = self_play
             r.out["explore"] = args.explore
+            r.out["collect"] = args.collect
             r.finish(st)
         return
     args.per, args.sp = int(args.per or 0), int(args.sp or 0)
