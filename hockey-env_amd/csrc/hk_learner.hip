@@ -19,6 +19,7 @@
 //                 grouped by policy on the device.
 //   explore       act with TD3.act's exploration (annealed noise, random phase) as the acting tile's epilogue.
 //   collect       what a training step does around the step kernel: the opponent draw and the replay store.
+//   eval          the evaluation loop's accounting for many (policy, opponent, seed) cells side by side, and its fold.
 //   value         twin-critic inference: Q_k(s, a), or V(s) = min Q_k(s, actor(s)) with the action kept in registers.
 //
 // The library's only translation unit: the kernels live in the headers below, included in the order of their
@@ -29,6 +30,7 @@
 #include "hkl_act.h"    // hkl_act / hkl_act_wide
 #include "hkl_explore.h"  // hkl_explore: hkl_act with the exploration epilogue
 #include "hkl_collect.h"  // hkl_opp_draw, hkl_collect
+#include "hkl_eval.h"   // hkl_eval_begin / hkl_eval_step / hkl_eval_fold
 #include "hkl_value.h"  // hkl_value
 
 using namespace hkl;
@@ -647,6 +649,51 @@ int hkl_collect(const hkl_collect_io *io, void *stream) {
   } else {
     hipLaunchKernelGGL(collect_store_kernel<false>, grid, dim3(CWG), 0, st, *io);
   }
+  return launched(who);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ C ABI: evaluation
+enum EvalCall { kEvalBegin, kEvalStep, kEvalFold };
+template <EvalCall K>
+static const char *bad_eval(const hkl_eval_io &io) {
+  if (io.rows_per_cell <= 0) return "rows_per_cell <= 0";
+  if (io.n_rows <= 0 || io.n_rows % io.rows_per_cell) return "n_rows is no positive multiple of rows_per_cell";
+  if (io.n_rows / io.rows_per_cell > HKL_EVAL_CELLS_MAX) return "n_cells (n_rows / rows_per_cell) outside [1, HKL_EVAL_CELLS_MAX]";
+  if (io.info_ld < 1) return "info_ld < 1";
+  if (!io.live || !io.ret || !io.length || !io.winner) return "null live / ret / length / winner";
+  if (K == kEvalFold) return (!io.outcomes || !io.length_sum || !io.return_sum) ? "null outcomes / length_sum / return_sum" : nullptr;
+  if (!io.seeds || !io.step || !io.count) return "null seeds / step / count";
+  return (K == kEvalStep && (!io.reward || !io.done || !io.info)) ? "null reward / done / info" : nullptr;
+}
+
+extern "C" {
+
+int hkl_eval_io_size(void) { return (int)sizeof(hkl_eval_io); }
+
+int hkl_eval_begin(const hkl_eval_io *io, void *stream) {
+  const char *who = "hkl_eval_begin";
+  if (const int rc = bad_io(who, io, bad_eval<kEvalBegin>)) return rc;
+  const dim3 grid(blocks(io->rows_per_cell, CWG), io->n_rows / io->rows_per_cell);
+  hipLaunchKernelGGL(eval_begin_kernel, grid, dim3(CWG), 0, (hipStream_t)stream, *io);
+  return launched(who);
+}
+
+int hkl_eval_step(const hkl_eval_io *io, void *stream) {
+  const char *who = "hkl_eval_step";
+  if (const int rc = bad_io(who, io, bad_eval<kEvalStep>)) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(blocks(io->rows_per_cell, CWG), io->n_rows / io->rows_per_cell);
+  hipLaunchKernelGGL(eval_step_kernel, grid, dim3(CWG), 0, st, *io);
+  hipLaunchKernelGGL(eval_advance_kernel, dim3(1), dim3(1), 0, st, *io);
+  return launched(who);
+}
+
+int hkl_eval_fold(const hkl_eval_io *io, void *stream) {
+  const char *who = "hkl_eval_fold";
+  if (const int rc = bad_io(who, io, bad_eval<kEvalFold>)) return rc;
+  hipLaunchKernelGGL(eval_fold_kernel, dim3(io->n_rows / io->rows_per_cell), dim3(CWG), 0, (hipStream_t)stream, *io);
   return launched(who);
 }
 

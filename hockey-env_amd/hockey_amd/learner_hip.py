@@ -19,7 +19,8 @@ the hkl_per_* kernels (per-block float64 sums; the slots come from the Philox st
 to 4 096 policies) are bound here and driven by ``hockey_amd.policy_bank.PolicyBank``; ``ValueIO`` / ``hkl_value`` (twin-critic inference) by
 ``hockey_amd.value.ValueFn``; ``ExploreIO`` / ``hkl_explore`` (acting with exploration) by ``hockey_amd.explore.Explorer``; ``OppDrawIO`` /
 ``hkl_opp_draw`` and ``CollectIO`` / ``hkl_collect`` (the opponent draw and the replay store of a collection step) by
-``hockey_amd.collect.Collector``.  The ``hkl_*_group`` forms (up to 64 independent learners per launch, each bit for bit
+``hockey_amd.collect.Collector``; ``EvalIO`` / ``hkl_eval_begin`` / ``hkl_eval_step`` / ``hkl_eval_fold`` (the evaluation
+loop's accounting) by ``hockey_amd.evaluator.Evaluator``.  The ``hkl_*_group`` forms (up to 64 independent learners per launch, each bit for bit
 its single call), ``hkl_per_*_group`` among them, are bound here and driven by
 ``hockey_amd.population.PopulationLearner`` and ``PopulationPrioritizedRing``.
 
@@ -157,6 +158,14 @@ class CollectIO(ctypes.Structure):
                 ("live", vp), ("keep_obs", vp), ("keep_obs2", vp), ("scratch", vp)]
 
 
+class EvalIO(ctypes.Structure):
+    """hkl_eval_io: the evaluation loop's accounting and its fold (hockey_amd.evaluator)."""
+    _fields_ = [("n_rows", ctypes.c_int32), ("rows_per_cell", ctypes.c_int32), ("info_ld", ctypes.c_int64),
+                ("seeds", vp), ("step", vp), ("reward", vp), ("done", vp), ("info", vp), ("live", vp), ("ret", vp),
+                ("length", vp), ("winner", vp), ("count", vp), ("opp_inc", vp), ("outcomes", vp), ("length_sum", vp),
+                ("return_sum", vp)]
+
+
 def act_wide_max_tiles(n_rows, n_policies):
     """The bound on the non-empty 64-row tiles of hkl_act_wide: its ``tiles`` scratch holds 3 int32 per tile."""
     return min(n_rows, -(-n_rows // 64) + n_policies)
@@ -186,6 +195,9 @@ EXPLORE_EXPORTS = ["hkl_explore", "hkl_explore_io_size", "hkl_explore_member_siz
 # include/hockey_collect.h (the opponent draw and the replay store), likewise
 COLLECT_EXPORTS = ["hkl_opp_draw", "hkl_opp_draw_io_size", "hkl_collect", "hkl_collect_io_size",
                    "hkl_collect_scratch_ints"]
+
+# include/hockey_eval.h (the evaluation loop's accounting and its fold), likewise
+EVAL_EXPORTS = ["hkl_eval_begin", "hkl_eval_step", "hkl_eval_fold", "hkl_eval_io_size"]
 
 _lib = None
 
@@ -222,6 +234,8 @@ def lib():
         L.hkl_collect.argtypes = [ctypes.POINTER(CollectIO), vp]
         L.hkl_collect_scratch_ints.argtypes = [ctypes.c_int32, ctypes.c_int32]
         L.hkl_collect_scratch_ints.restype = ctypes.c_int64
+        for name in ("hkl_eval_begin", "hkl_eval_step", "hkl_eval_fold"):
+            getattr(L, name).argtypes = [ctypes.POINTER(EvalIO), vp]
         # grouped forms: (host array, the same bytes on the device, ..., n_members, stream)
         L.hkl_sample_group.argtypes = [ctypes.POINTER(SampleIO), vp, ctypes.c_int, vp]
         L.hkl_critic_step_group.argtypes = [ctypes.POINTER(CriticIO), vp, ctypes.c_int, vp]
@@ -250,6 +264,8 @@ def lib():
         if (L.hkl_opp_draw_io_size() != ctypes.sizeof(OppDrawIO)
                 or L.hkl_collect_io_size() != ctypes.sizeof(CollectIO)):
             raise _native.HockeyNativeError("libhockey_learner.so hkl_collect_io differs from hockey_amd.learner_hip")
+        if L.hkl_eval_io_size() != ctypes.sizeof(EvalIO):
+            raise _native.HockeyNativeError("libhockey_learner.so hkl_eval_io differs from hockey_amd.learner_hip")
         _lib = L
     return _lib
 

@@ -365,7 +365,8 @@ def _check_members(members, per_ok=False, self_play_ok=False):
 
 def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode.NORMAL, episode_end="max_steps",
                      updates_per_round=None, eval_fn=None, on_step=None, env=None, replay_capacity=None, graphs=True,
-                     log=None, timing=False, self_play=None, explore="torch", collect="torch", poll_every=16):
+                     log=None, timing=False, self_play=None, explore="torch", collect="torch", poll_every=16,
+                     evaluator=None):
     """``hockey_amd.td3.train`` for S = len(members) agents side by side in one process.  ``members`` is a list of
     (TD3Config, seed) or (TD3Config, seed, resume_from); member j owns arenas [j n, (j + 1) n) of one VecHockeyEnv of
     S * n_arenas arenas (``env``: a ready batch of that many arenas, e.g. the kernel source's host build in the CPU
@@ -419,6 +420,11 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
     running arenas.  Every draw of collection is then keyed by the member's seed: member j's trajectories, ring and
     weights are the same bits alone and in any population (hockey_amd.collect lists the batched differences).
 
+    evaluator: a callable such as ``hockey_amd.evaluator.PopulationEval``, called once per due evaluation -- where
+    ``eval_fn`` would be called once per member -- as ``evaluator(agents, bank, episodes)`` with the acting bank (slot j
+    holds member j's actor, refreshed after the round's updates); its one record per member is appended to
+    ``stats[j]["evals"]``.  Passing both ``eval_fn`` and ``evaluator`` raises ValueError.
+
     Collection randomness is shared under collect="torch": the exploration and opponent draws (bot or self-play, which bot, and with
     ``self_play`` which snapshot) come from torch generators of the whole population and the step kernel's device
     draws are keyed by the global arena id.  The self-play pools, their scores and their snapshot schedule are per
@@ -438,6 +444,8 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
         raise ValueError("explore must be 'torch' or 'device'")
     if collect not in ("torch", "device"):
         raise ValueError("collect must be 'torch' or 'device'")
+    if eval_fn is not None and evaluator is not None:
+        raise ValueError("pass eval_fn (one call per member) or evaluator (one call per evaluation), not both")
     if collect == "device":
         if explore != "device":
             raise ValueError("collect='device' runs behind hkl_explore: it needs explore='device'")
@@ -622,6 +630,9 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
         if eval_fn is not None and clock.eval_due(episodes):
             for j, ag in enumerate(agents):
                 stats[j]["evals"].append(eval_fn(ag, episodes))
+        if evaluator is not None and clock.eval_due(episodes):
+            for j, rec in enumerate(evaluator(agents, bank, episodes)):
+                stats[j]["evals"].append(rec)
         if log:
             log(rnd, stats)
     if own_env:

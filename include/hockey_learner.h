@@ -307,6 +307,10 @@ int hkl_act(const hkl_act_io *io, void *stream);
  * their own beside the exploration's. */
 #include "hockey_collect.h"
 
+/* ---- evaluation on the device: the accounting of the evaluation loop for many cells side by side and its fold, in a
+ * header of their own beside the collection's. */
+#include "hockey_eval.h"
+
 /* ---- actor inference over a wide bank (population self-play: one pool of snapshots per member) ----
  * hkl_act's contract with K = n_policies in [1, HKL_ACT_WIDE_MAX_POLICIES]: params, packs, obs, policy and out as
  * above, a row with policy[i] outside [0, K) is not written, no other float of out is, and a row's four actions are

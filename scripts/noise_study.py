@@ -26,7 +26,10 @@ Writes <out>/<protocol>_<noise>_s<seed>.json after every evaluation and the best
 cells x ``--seeds``, or the cells ``--per`` / ``--sp`` leave open; self-play members keep their own pools and play
 them per arena, train_population(self_play="arena")) as the members of ONE process (hockey_amd.population: grouped
 learner kernels, one env of members x arenas arenas) and writes the same per-run files; the members' collection
-randomness is then shared (train_population docstring), each member's learner stream stays its own.
+randomness is then shared (train_population docstring), each member's learner stream stays its own.  ``--eval device``
+plays each evaluation of all members as one batch of arenas (hockey_amd.evaluator.PopulationEval, seed = the member's)
+and all runs' final re-evaluation as one ``evaluate_many``; the record and the best-checkpoint rule are the serial
+path's, and each run's JSON carries ``"eval": "device"``.
 
 Usage: python scripts/noise_study.py --protocol stage2 --noise gaussian --seed 42 --out gpurun_out/r05/noise
        python scripts/noise_study.py --protocol stage2 --population --seeds 42,43,44 --out OUT_DIR
@@ -129,6 +132,10 @@ def main():
                     help="--population: the rest of a collection step, train_population(collect=...); 'device' (needs "
                          "--explore device) is hkl_opp_draw + hkl_collect around the step kernel, every draw keyed by "
                          "the member's own seed: a member's run no longer depends on the population")
+    ap.add_argument("--eval", choices=["serial", "device"], default="serial",
+                    help="--population: 'device' plays every member's evaluation games as one batch "
+                         "(hockey_amd.evaluator.PopulationEval, seed = the member's) and all runs' final "
+                         "re-evaluation as one evaluate_many; 'serial' is two evaluate() calls per member")
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "noise_study"))
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
@@ -149,20 +156,45 @@ def main():
         by_member = {key(r.cfg, r.seed): r for r in runs}
         members = [(r.cfg, r.seed, r.resume) if r.resume else (r.cfg, r.seed) for r in runs]
         self_play = "arena" if any(r.cfg.use_self_play for r in runs) else None
+        hooks = dict(eval_fn=lambda ag, ep: by_member[key(ag.cfg, ag.seed)].eval_fn(ag, ep))
+        if args.eval == "device":
+            from hockey_amd.evaluator import PopulationEval, evaluate_many
+
+            pop_eval = PopulationEval(len(runs), episodes=args.eval_episodes)
+            for r in runs:
+                r.out["eval"] = "device"
+
+            def evaluator(agents, bank, episodes):  # one batch; then each run's record and best-checkpoint rule
+                return [by_member[key(ag.cfg, ag.seed)].record(ag, episodes, e["wr_strong"], e["wr_weak"],
+                                                               e["r_strong"], e["r_weak"])
+                        for ag, e in zip(agents, pop_eval(agents, bank, episodes))]
+
+            hooks = dict(evaluator=evaluator)
         _, stats = train_population(members, n_arenas=n, rounds=rounds, device="cuda:0", episode_end="done",
-                                    eval_fn=lambda ag, ep: by_member[key(ag.cfg, ag.seed)].eval_fn(ag, ep),
-                                    self_play=self_play, explore=args.explore, collect=args.collect)
+                                    self_play=self_play, explore=args.explore, collect=args.collect, **hooks)
         torch.cuda.synchronize()
-        for r, st in zip(runs, stats):
+        finals = [None] * len(runs)
+        if args.eval == "device":  # every run's best actor x 2 bots x --final-games in one batch
+            pop_eval.close()
+            have = [k for k, r in enumerate(runs) if r.best_actor() is not None]
+            if have:
+                fe = evaluate_many([runs[k].best_actor() for k in have], episodes=args.final_games, seeds=100_000,
+                                   opponents=("strong", "weak"), device="cuda:0")
+                for i, k in enumerate(have):
+                    finals[k] = {opp: {m: float(fe[m][i, o]) for m in ("win", "mean_return", "draw", "mean_length")}
+                                 for o, opp in enumerate(("strong", "weak"))}
+        for r, st, fin in zip(runs, stats, finals):
             r.out["population"] = len(runs)  # collect="torch": the members share collection randomness
             r.out["self_play_sampling"] = self_play
             r.out["explore"] = args.explore
             r.out["collect"] = args.collect
-            r.finish(st)
+            r.finish(st, fin)
         return
     args.per, args.sp = int(args.per or 0), int(args.sp or 0)
     if args.noise is None:
         ap.error("--noise is required without --population")
+    if args.eval == "device":
+        ap.error("--eval device needs --population")
     run = Run(args, args.noise, args.seed)
     fused = {"auto": "auto", "fused": True, "eager": False}[args.learner]
     agent, st = train(n_arenas=n, rounds=rounds, cfg=run.cfg, device="cuda:0", seed=args.seed, eval_fn=run.eval_fn,
@@ -199,14 +231,19 @@ class Run:
             json.dump(self.out, f, indent=1)
 
     def eval_fn(self, agent, episodes):
-        args, dev, best, out = self.args, self.dev, self.best, self.out
+        args, dev = self.args, self.dev
         agent.actor.eval()
         s = evaluate(agent.actor, episodes=args.eval_episodes, seed=agent.seed, weak_opponent=False, device=dev)
         w = evaluate(agent.actor, episodes=args.eval_episodes, seed=agent.seed, weak_opponent=True, device=dev)
         agent.actor.train()
-        score = min(s["win"], w["win"])  # rl/training/train.py:228
-        rec = {"episode": episodes, "updates": agent.train_step, "wr_strong": s["win"], "wr_weak": w["win"],
-               "r_strong": s["mean_return"], "r_weak": w["mean_return"], "score": score,
+        return self.record(agent, episodes, s["win"], w["win"], s["mean_return"], w["mean_return"])
+
+    def record(self, agent, episodes, wr_strong, wr_weak, r_strong, r_weak):
+        """One evaluation's record and the best-checkpoint rule, whichever path played the games."""
+        best, out = self.best, self.out
+        score = min(wr_strong, wr_weak)  # rl/training/train.py:228
+        rec = {"episode": episodes, "updates": agent.train_step, "wr_strong": wr_strong, "wr_weak": wr_weak,
+               "r_strong": r_strong, "r_weak": r_weak, "score": score,
                "noise_scale": agent.current_noise_scale, "wall_s": round(time.time() - self.t0, 1)}
         if score > best["score"] + 0.01:  # rl/utils/model_manager.py:15-23
             best.update(score=score, state={k: v.detach().clone() for k, v in agent.actor.state_dict().items()})
@@ -218,16 +255,25 @@ class Run:
         print(json.dumps(rec), flush=True)
         return rec
 
-    def finish(self, st):
-        args, dev, best, out = self.args, self.dev, self.best, self.out
+    def best_actor(self):
+        """The best checkpoint's actor, or None before the first evaluation."""
+        if "state" not in self.best:
+            return None
+        actor = Actor().to(self.dev)
+        actor.load_state_dict(self.best["state"])
+        return actor.eval()
+
+    def finish(self, st, final=None):
+        """final: the re-evaluation's {"strong": r, "weak": r} (win / mean_return / draw / mean_length) when the caller
+        has played it (--eval device: all runs in one batch); None plays it here, one evaluate() per bot."""
+        args, dev, out = self.args, self.dev, self.out
         out.update(updates=st["updates"], env_steps=st["env_steps"], train_wall_s=round(time.time() - self.t0, 1))
-        if "state" in best:
-            actor = Actor().to(dev)
-            actor.load_state_dict(best["state"])
-            actor.eval()
+        actor = self.best_actor()
+        if actor is not None:
             fin = {}
             for opp in ("strong", "weak"):
-                r = evaluate(actor, episodes=args.final_games, seed=100_000, weak_opponent=opp == "weak", device=dev)
+                r = final[opp] if final is not None else evaluate(actor, episodes=args.final_games, seed=100_000,
+                                                                  weak_opponent=opp == "weak", device=dev)
                 fin[f"wr_{opp}"], fin[f"r_{opp}"] = r["win"], r["mean_return"]
                 fin[f"draw_{opp}"], fin[f"len_{opp}"] = r["draw"], r["mean_length"]
             fin["games"] = args.final_games
