@@ -49,7 +49,9 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .explore import GROUP_MAX, _LO, _S32, _U64, draw_words
+from .explore import GROUP_MAX
+from .philox_ref import U64, draw_words, phase_inc, u24, u53  # noqa: F401 (u53: re-exported)
+from .policy_bank import resolve_backend
 
 KEY_OPP = 0x6F70706F6E656E74  # HKL_COLLECT_KEY_OPP ("opponent")
 KEY_PHASE = 0x7068617365  # HKL_COLLECT_KEY_PHASE ("phase")
@@ -57,17 +59,6 @@ PHASE_TAG = 0x626F7473  # "bots": the host generator of a member's phases in a r
 
 
 # ---------------------------------------------------------------------------------------------------- the laws in numpy
-def u24(words):
-    """(w >> 8) 2^-24 in float32 (exact)."""
-    return (words >> 8).astype(np.float32) * np.float32(2.0 ** -24)
-
-
-def u53(a, b):
-    """(((a << 32) | b) >> 11) 2^-53 in float64 (exact): hkl_sample's uniform."""
-    bits = ((a.astype(np.uint64) << _S32) | (b.astype(np.uint64) & _LO)) >> np.uint64(11)
-    return bits.astype(np.float64) * 2.0 ** -53
-
-
 def opp_draw_law(seeds, n, calls, probs, lens, scores, slots, alive=None, counts=None, snap_counts=None):
     """One ``hkl_opp_draw`` call in numpy.  seeds [S] ints; calls [S] int64 (the state before the call); probs [S, 2]
     float32 (p_self, p_strong); lens [S] int32; scores [S, P] float32; slots [S, P] int32; alive [S n] or None; counts
@@ -102,8 +93,7 @@ def opp_draw_law(seeds, n, calls, probs, lens, scores, slots, alive=None, counts
             policy[rows] = np.where(sp, slots[m, k], -1)
             snap[rows] = np.where(sp, m * P + k, -1)
             np.add.at(snap_counts, (m * P + k)[sp & live[rows]], 1)
-        q = draw_words(seeds[m], KEY_PHASE, n, calls[m])
-        inc[rows, 0], inc[rows, 1] = 0.2 * u53(q[:, 0], q[:, 1]), 0.2 * u53(q[:, 2], q[:, 3])
+        inc[rows] = phase_inc(draw_words(seeds[m], KEY_PHASE, n, calls[m]))
         lv = live[rows]
         counts[m] += [int((strong & lv).sum()), int((~sp & ~strong & lv).sum()), int((sp & lv).sum())]
         calls[m] += 1
@@ -153,10 +143,21 @@ def collect_law(n, cap, reward, done, snap, alive, pos, size, ep_reward, steps, 
     return out
 
 
+def clear_episode_words(env, n_rows, device, zeros=None):
+    """Clear the episode words of an env's ``n_rows`` arenas (``set_state(aux=0)``: the has-puck timers, time, done,
+    winner), which a reset carries over from the games before.  An env without ``set_state`` is left as it is.
+    Returns the zero words it used, for the caller to keep and pass back as ``zeros`` (the copy is asynchronous)."""
+    if hasattr(env, "set_state"):
+        if zeros is None:
+            zeros = torch.zeros((n_rows, N.AUX_DIM), dtype=torch.int32, device=device)
+        env.set_state(aux=zeros)
+    return zeros
+
+
 def phase_rows(seed, n, rnd=0):
     """The three BasicOpponent starting phases of a member's n arenas in its round ``rnd``: U(0, pi) from a generator
     of the member's own."""
-    return np.random.default_rng([int(seed) & _U64, PHASE_TAG, int(rnd)]).uniform(0.0, math.pi, (int(n), 3))
+    return np.random.default_rng([int(seed) & U64, PHASE_TAG, int(rnd)]).uniform(0.0, math.pi, (int(n), 3))
 
 
 # ---------------------------------------------------------------------------------------------------- Collector
@@ -178,10 +179,8 @@ class Collector:
 
     def __init__(self, env, bank, mix, ring, explorer, members, rows_per_member, backend="auto",
                  episode_end="max_steps", poll_every=16):
-        from .policy_bank import _hip_ready
-
         self.env, self.bank, self.mix, self.ring, self.explorer = env, bank, mix, ring, explorer
-        self.seeds = [int(getattr(m, "seed", m)) & _U64 for m in members]
+        self.seeds = [int(getattr(m, "seed", m)) & U64 for m in members]
         S, n = len(self.seeds), int(rows_per_member)
         if not 1 <= S <= GROUP_MAX:
             raise ValueError(f"a Collector has 1 to {GROUP_MAX} members, got {S}")
@@ -193,13 +192,11 @@ class Collector:
             raise ValueError("the Collector draws a snapshot per arena and step: the mix must have sampling='arena'")
         if episode_end not in ("max_steps", "done"):
             raise ValueError("episode_end must be 'max_steps' or 'done'")
-        if backend not in ("auto", "hip", "torch"):
-            raise ValueError("backend must be 'auto', 'hip' or 'torch'")
+        dev = self.device = torch.device(ring.device)
+        self.backend = resolve_backend(backend, dev)
         if int(poll_every) < 1:
             raise ValueError("poll_every must be positive")
         self.S, self.n, self.N, self.P = S, n, S * n, int(mix.pmax)
-        dev = self.device = torch.device(ring.device)
-        self.backend = ("hip" if _hip_ready(dev) else "torch") if backend == "auto" else backend
         self.stop_at_done, self.poll_every = episode_end == "done", int(poll_every)
         self.prioritized = hasattr(ring, "pers")
         NN, P = self.N, self.P
@@ -284,10 +281,7 @@ class Collector:
             self.calls.copy_(self._calls0 + self.live)
             if self.explorer is not None:
                 self.explorer.calls.copy_(self._ecalls0 + self.live)
-            if hasattr(self.env, "set_state"):  # what the env's reset carries over: the has-puck timers
-                if self._aux0 is None:
-                    self._aux0 = torch.zeros((self.N, N.AUX_DIM), dtype=torch.int32, device=self.device)
-                self.env.set_state(aux=self._aux0)
+            self._aux0 = clear_episode_words(self.env, self.N, self.device, self._aux0)
         mix = self.mix
         mix._counts, mix._snap_counts = self.counts.clone(), self.snap_counts.clone()
         mix._outcomes = list(self.tally[:self.t].unbind(0)) if self.any_pool else []

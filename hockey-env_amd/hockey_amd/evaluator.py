@@ -37,10 +37,11 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .collect import u53
+from .collect import clear_episode_words
 from .constants import Mode
 from .evaluate import reset_params, tournament_pairs
-from .explore import _U64, draw_words
+from .philox_ref import U64, draw_words, phase_inc
+from .policy_bank import resolve_backend
 
 KEY_PHASE = 0x6576616C70686173  # HKL_EVAL_KEY_PHASE ("evalphas")
 CELLS_MAX = 65535  # HKL_EVAL_CELLS_MAX
@@ -51,8 +52,7 @@ _BOTS = {"weak": N.POLICY_BASIC_WEAK, "strong": N.POLICY_BASIC_STRONG}
 # ---------------------------------------------------------------------------------------------------- the laws in numpy
 def eval_inc(seed, n, t):
     """inc(c, local, t) for local = 0 .. n - 1 of a cell with ``seed``: float64 [n, 2]."""
-    w = draw_words(seed, KEY_PHASE, n, t)
-    return np.stack([0.2 * u53(w[:, 0], w[:, 1]), 0.2 * u53(w[:, 2], w[:, 3])], 1)
+    return phase_inc(draw_words(seed, KEY_PHASE, n, t))
 
 
 def eval_begin_law(seeds, n):
@@ -126,23 +126,19 @@ class Evaluator:
 
     def __init__(self, n_cells, episodes, replicas=1, mode=Mode.NORMAL, device="cuda:0", backend="auto", poll_every=16,
                  env=None):
-        from .policy_bank import _hip_ready
-
         self.C, self.episodes, self.replicas = int(n_cells), int(episodes), int(replicas)
         if not 1 <= self.C <= CELLS_MAX:
             raise ValueError(f"an Evaluator has 1 to {CELLS_MAX} cells, got {n_cells}")
         if self.episodes < 1 or self.replicas < 1:
             raise ValueError("episodes and replicas must be positive")
-        if backend not in ("auto", "hip", "torch"):
-            raise ValueError("backend must be 'auto', 'hip' or 'torch'")
+        dev = self.device = torch.device(device)
+        self.backend = resolve_backend(backend, dev)
         if int(poll_every) < 1:
             raise ValueError("poll_every must be positive")
         self.n = self.episodes * self.replicas
         self.N = self.C * self.n
         if self.N >= 1 << 31:
             raise ValueError("n_cells x episodes x replicas must be below 2**31")
-        dev = self.device = torch.device(device)
-        self.backend = ("hip" if _hip_ready(dev) else "torch") if backend == "auto" else backend
         if self.backend == "hip" and dev.type != "cuda":
             raise N.HockeyNativeError("Evaluator backend='hip' runs on the GPU only")
         self.mode, self.poll_every = mode, int(poll_every)
@@ -168,8 +164,7 @@ class Evaluator:
         self.return_sum = self._fold[5 * C:].view(torch.float64)
         self.act8 = z((NN, 8), torch.float32)
         self.pol1, self.pol2, self.policy2 = z(NN, torch.int32), z(NN, torch.int32), z(NN, torch.uint8)
-        self._aux0 = None
-        self._io = None
+        self._aux0 = self._io = None
         self.steps = 0  # the env steps of the last run
 
     def close(self):
@@ -240,10 +235,7 @@ class Evaluator:
         """The placements and the bots' starting phases of every cell; returns the mode's max_timesteps."""
         env, n, E = self.env, self.n, self.episodes
         e = np.tile(np.arange(E, dtype=np.int64), self.replicas)  # game g = r E + e plays placement e
-        if hasattr(env, "set_state"):  # what a reset carries over from the games before: the has-puck timers
-            if self._aux0 is None:
-                self._aux0 = torch.zeros((self.N, N.AUX_DIM), dtype=torch.int32, device=self.device)
-            env.set_state(aux=self._aux0)
+        self._aux0 = clear_episode_words(env, self.N, self.device, self._aux0)
         if self.own_env:
             rows = np.concatenate([np.array([int(s) + int(k) for k in e], dtype=object) for s in seeds])
             env.reset_seeded(list(rows), one_starting=np.tile((e % 2) == 1, self.C))
@@ -290,7 +282,7 @@ class Evaluator:
         self.pol1.copy_(torch.from_numpy(np.repeat(np.array(p1, np.int32), n)))
         self.pol2.copy_(torch.from_numpy(np.repeat(np.array(slot2, np.int32), n)))
         self.policy2.copy_(torch.from_numpy(np.repeat(np.array(ids, np.uint8), n)))
-        self._seeds = [s & _U64 for s in seeds]
+        self._seeds = [s & U64 for s in seeds]
         self.seeds_t.copy_(torch.from_numpy(np.array(self._seeds, np.uint64).view(np.int64)))
         any_slot = any(k >= 0 for k in slot2)
         env = self.env

@@ -38,6 +38,8 @@ import numpy as np
 import torch
 
 from .noise import pink_block
+from .philox_ref import U64, draw_words, normals, philox4x32_10, uniform_pm1  # noqa: F401 (philox4x32_10: re-exported)
+from .policy_bank import resolve_backend
 
 KEY_NOISE = 0x6578706C6F7265  # HKL_EXPLORE_KEY_NOISE ("explore")
 KEY_RANDOM = 0x72616E646F6D  # HKL_EXPLORE_KEY_RANDOM ("random")
@@ -46,7 +48,6 @@ NOISE = {"none": 0, "gaussian": 1, "uniform": 2, "ornstein-uhlenbeck": 3, "exter
 _NONE, _GAUSS, _UNIFORM, _OU, _EXT = range(5)
 GROUP_MAX = 64  # HKL_GROUP_MAX
 SQRT3 = np.float32(math.sqrt(3.0))
-_U64 = (1 << 64) - 1
 
 
 @dataclass
@@ -88,49 +89,6 @@ class Member:
 
 
 # ---------------------------------------------------------------------------------------------------- the law in numpy
-_M0, _M1, _W0, _W1, _LO, _S32 = (np.uint64(0xD2511F53), np.uint64(0xCD9E8D57), np.uint64(0x9E3779B9),
-                                 np.uint64(0xBB67AE85), np.uint64(0xFFFFFFFF), np.uint64(32))
-
-
-def philox4x32_10(key, counter):
-    """Philox4x32-10: key (uint64: low word k0, high word k1) and counter [..., 4] uint32 words -> [..., 4] uint32."""
-    key = np.asarray(key, dtype=np.uint64)
-    c = np.asarray(counter).astype(np.uint64)
-    k0, k1 = key & _LO, key >> _S32
-    c0, c1, c2, c3 = (c[..., i] for i in range(4))
-    for _ in range(10):
-        p0, p1 = _M0 * c0, _M1 * c2  # 32 x 32 -> 64 bits
-        c0, c1, c2, c3 = (p1 >> _S32) ^ c1 ^ k0, p1 & _LO, (p0 >> _S32) ^ c3 ^ k1, p0 & _LO
-        k0, k1 = (k0 + _W0) & _LO, (k1 + _W1) & _LO
-    return np.stack([c0, c1, c2, c3], -1).astype(np.uint32)
-
-
-def draw_words(seed, purpose, n, calls):
-    """The Philox blocks [n, 4] of a member's rows local = 0 .. n - 1 at call counter ``calls``."""
-    loc = np.arange(n, dtype=np.uint64)
-    calls = np.uint64(int(calls) & _U64)
-    ctr = np.stack([loc & _LO, loc >> _S32, np.full(n, calls & _LO), np.full(n, calls >> _S32)], -1)
-    return philox4x32_10(np.uint64((int(seed) & _U64) ^ purpose), ctr)
-
-
-def uniform_pm1(words):
-    """2 u - 1 with u = (w >> 8) 2^-24, in float32 (exact)."""
-    return np.float32(2.0) * ((words >> 8).astype(np.float32) * np.float32(2.0 ** -24)) - np.float32(1.0)
-
-
-def normals(words, dtype=np.float32):
-    """The four Box-Muller normals of each block (hkl_sample's construction), evaluated in ``dtype``."""
-    f = np.dtype(dtype).type
-    z = np.zeros(words.shape, dtype)
-    for p in range(2):
-        u1 = ((words[:, 2 * p] >> 8).astype(dtype) + f(0.5)) * f(2.0 ** -24)
-        u2 = (words[:, 2 * p + 1] >> 8).astype(dtype) * f(2.0 ** -24)
-        rad = np.sqrt(f(-2.0) * np.log(u1))
-        ang = f(np.float32(2.0 * np.pi)) * u2  # the kernel's angle constant is the float32 2 pi
-        z[:, 2 * p], z[:, 2 * p + 1] = rad * np.cos(ang), rad * np.sin(ang)
-    return z
-
-
 def noise_scale(mem, t1):
     """float32(TD3.noise_scale()) at total_steps = t1 for ``mem``."""
     s = float(mem.init_scale)
@@ -200,10 +158,10 @@ class Explorer:
     The state -- ``total`` / ``calls`` [S] int64, the OU state ``x`` [N, 4], the pink blocks -- lives on ``device``;
     ``scale`` [S] receives the float32 scale of the last call and, with keep_draws, ``z`` [N, 4] its raw draws."""
 
+    count_on_device = True  # a collector hands ``explore`` the running arenas as int32 [S] on the device
+
     def __init__(self, bank, members, rows_per_member, device=None, backend="auto", policy="member",
                  keep_draws=False):
-        from .policy_bank import _hip_ready
-
         self.bank = bank
         self.members = [m.check() for m in members]
         S, n = len(self.members), int(rows_per_member)
@@ -215,9 +173,7 @@ class Explorer:
         dev = self.device = torch.device(bank.device if device is None else device)
         if dev != bank.device:
             raise ValueError(f"the Explorer is on {dev}, its bank on {bank.device}")
-        if backend not in ("auto", "hip", "torch"):
-            raise ValueError("backend must be 'auto', 'hip' or 'torch'")
-        self.backend = ("hip" if _hip_ready(dev) else "torch") if backend == "auto" else backend
+        self.backend = resolve_backend(backend, dev)
         if isinstance(policy, str):
             if policy != "member":
                 raise ValueError("policy must be 'member' or an int32 tensor")
@@ -248,7 +204,7 @@ class Explorer:
 
             self._host = (LH.ExploreMember * S)()
             for h, m in zip(self._host, self.members):
-                h.seed, h.start_steps, h.max_total_steps = m.seed & _U64, m.start_steps, m.max_total_steps
+                h.seed, h.start_steps, h.max_total_steps = m.seed & U64, m.start_steps, m.max_total_steps
                 h.init_scale, h.min_scale, h.anneal, h.noise = m.init_scale, m.min_scale, ANNEAL[m.anneal], NOISE[m.noise]
                 h.theta, h.dt, h.sqrt_dt = m.theta, m.dt, math.sqrt(m.dt)
             self._dev = LH.upload(self._host, dev)
@@ -274,6 +230,14 @@ class Explorer:
     def total_steps(self):
         """The members' ``total_steps`` as a list of ints: the one read-back, for the end of a round."""
         return self.total.cpu().tolist()
+
+    def sync(self, agents):
+        """At a round's end: every agent's ``total_steps`` from the device counters (one read-back) and its
+        ``current_noise_scale`` as ``TD3.act`` would have left it (updated by every step past the all-random phase)."""
+        for ag, t in zip(agents, self.total_steps()):
+            ag.total_steps = int(t)
+            if ag.total_steps >= ag.cfg.start_steps:
+                ag.current_noise_scale = ag.noise_scale()
 
     def _ext_view(self, ext):
         """(tensor, row stride, column stride) of this call's external unit noise, or None."""
@@ -350,13 +314,6 @@ class Explorer:
         self.calls.copy_(new["calls"])
 
 
-def sync_agents(explorer, agents):
-    """At a round's end: every agent's ``total_steps`` from the device counters (one read-back) and its
-    ``current_noise_scale`` as ``TD3.act`` would have left it (updated by every step past the all-random phase)."""
-    for ag, t in zip(agents, explorer.total_steps()):
-        ag.total_steps = int(t)
-        if ag.total_steps >= ag.cfg.start_steps:
-            ag.current_noise_scale = ag.noise_scale()
-
+sync_agents = Explorer.sync  # sync_agents(explorer, agents)
 
 __all__ = ["Explorer", "Member", "law", "philox4x32_10", "sync_agents", "KEY_NOISE", "KEY_RANDOM"]

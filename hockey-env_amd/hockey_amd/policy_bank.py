@@ -50,6 +50,15 @@ def _hip_ready(device):
     return device.type == "cuda" and fused_available()
 
 
+def resolve_backend(backend, device):
+    """``backend`` checked, with "auto" turned into "hip" on a GPU when the learner library is built, else "torch"."""
+    if backend not in ("auto", "hip", "torch"):
+        raise ValueError("backend must be 'auto', 'hip' or 'torch'")
+    if backend == "auto":
+        backend = "hip" if _hip_ready(device) else "torch"
+    return backend
+
+
 class PolicyBank:
     """Up to ``capacity`` actors acting side by side (module docstring)."""
 
@@ -219,10 +228,7 @@ class PolicyBank:
         policy=None: every row runs slot 0 (the single-actor case, nothing is grouped).  out=None: a new zero
         [n, out_col + 4] tensor.  Rows whose policy names a free slot are undefined under "hip" (the slot's last
         weights) and untouched under "torch".  Returns ``out``."""
-        if backend not in ("auto", "hip", "torch"):
-            raise ValueError("backend must be 'auto', 'hip' or 'torch'")
-        if backend == "auto":
-            backend = "hip" if _hip_ready(self.device) else "torch"
+        backend = resolve_backend(backend, self.device)
         if obs.dim() != 2 or obs.shape[1] < 18 or obs.dtype != torch.float32:
             raise ValueError(f"obs must be float32 [n, >= 18], got {obs.dtype} {tuple(obs.shape)}")
         if obs.device != self.device:

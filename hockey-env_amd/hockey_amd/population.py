@@ -35,8 +35,8 @@ import torch
 from . import learner_hip as LH
 from .constants import Mode
 from .learner_hip import GROUP_MAX
-from .noise import make_noise
-from .td3 import TD3, Learner, PairRunner, PerBlocks, ReplayRing, RoundClock, reset_round, store_step, updates_for
+from .host_round import PopulationExplorer, TorchCollector, check_collect_args
+from .td3 import TD3, Learner, PairRunner, PerBlocks, ReplayRing, RoundClock, reset_round, updates_for
 
 
 # ---------------------------------------------------------------------------------------------------- replay
@@ -374,12 +374,6 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
 
     * Player 1 acts through a PolicyBank of S slots with policy[i] = i // n: one ``hkl_act`` launch per step.  The
       bank is refreshed from the members' actors after each round's updates: actors only change there.
-    * Exploration restates ``TD3.act`` per arena: each member's total_steps advances by its running arenas, its
-      annealed scale is ``TD3.noise_scale()`` of that count, and arena i of the member draws a uniform action while
-      (total_steps before the step + 1 + i) < start_steps or the whole step lies in the random phase.  The per-member
-      counts, start_steps and scales are [S] tensors on the device; there is one noise generator per distinct
-      ``noise_mode`` over that mode's arenas (unit scale, seeded by the mode's first member), multiplied by the
-      arena's scale, and it advances on every step in which one of its members is past the all-random phase.
     * Player 2 is one OpponentMix over all arenas (seeded by member 0), so the members share ``curriculum_name``,
       ``max_steps`` and ``train_iters`` (and batch_size, policy_update_freq, buffer_size, eval_interval).
     * ``self_play``: None (the default) refuses a member with self-play (use_self_play and a self-play share in the
@@ -401,35 +395,19 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
     * on_step(member_of_row, arena_of_row, obs, action, reward, next_obs, done, step_result) sees every stored
       transition of a step, ragged over the members (test hook).
 
-    explore: "torch" (default) is the exploration described above.  "device" acts through one
-    ``hockey_amd.explore.Explorer`` over the S members: ONE ``hkl_explore`` call per step runs the bank, the members'
-    schedules, their noise and the random phase and writes player 1's columns of the step kernel's input; the members'
-    step counts live on the device (``episode_end="done"``: the running arenas are counted there) and reach
-    ``agent.total_steps`` / ``current_noise_scale`` at the end of a round.  Member j's exploration draws are then keyed by
-    its own seed, its arenas' indices inside the member and its own call counter: they do not depend on the population
-    (the opponent draws and the step kernel's draws still do).
-
-    collect: "torch" (default) is the collection described above.  "device" (needs explore="device"; self_play None or
-    "arena"; no on_step) runs every step through one ``hockey_amd.collect.Collector``: after ``hkl_explore``, one
-    ``hkl_opp_draw`` (bot or self-play, which bot, which snapshot, the bots' phase increments, the opponent counts), one
-    ``PolicyBank.act`` for the self-play arenas, the step kernel and one ``hkl_collect`` (the ragged replay store, write
-    positions, episode rewards, outcome tally, survivors), then ``hkl_per_push_group`` for prioritized members -- no torch
-    op on an [N]-row tensor in between and nothing read back but, under episode_end="done", the survivors' count every
-    ``poll_every`` steps (the results do not depend on it).  Player 2 is then always a ``PopulationOpponentMix`` (without
-    ``self_play`` one whose members keep no pools) and ``stats[j]["opponents"]`` member j's own counts, taken over its
-    running arenas.  Every draw of collection is then keyed by the member's seed: member j's trajectories, ring and
-    weights are the same bits alone and in any population (hockey_amd.collect lists the batched differences).
+    explore / collect: "torch" (default) or "device": where exploration and the rest of a collection step run
+    (hockey_amd.host_round states both, with the collectors).  collect="device" needs explore="device", self_play None
+    or "arena" and no on_step; player 2 is then always a ``PopulationOpponentMix`` (without ``self_play`` one whose
+    members keep no pools) and ``stats[j]["opponents"]`` member j's own counts, taken over its running arenas.
+    poll_every: collect="device"'s steps between two reads of the survivors' count.
 
     evaluator: a callable such as ``hockey_amd.evaluator.PopulationEval``, called once per due evaluation -- where
     ``eval_fn`` would be called once per member -- as ``evaluator(agents, bank, episodes)`` with the acting bank (slot j
     holds member j's actor, refreshed after the round's updates); its one record per member is appended to
     ``stats[j]["evals"]``.  Passing both ``eval_fn`` and ``evaluator`` raises ValueError.
 
-    Collection randomness is shared under collect="torch": the exploration and opponent draws (bot or self-play, which bot, and with
-    ``self_play`` which snapshot) come from torch generators of the whole population and the step kernel's device
-    draws are keyed by the global arena id.  The self-play pools, their scores and their snapshot schedule are per
-    member.  A member's trajectory therefore
-    depends on its position in the population and on its size; only the learner is composition-independent (module
+    Collection randomness is shared under collect="torch" (hockey_amd.host_round); the self-play pools, their scores
+    and their snapshot schedule are per member.  Only the learner is composition-independent there (module
     docstring)."""
     from .opponents import OpponentMix, PopulationOpponentMix
     from .policy_bank import PolicyBank
@@ -440,24 +418,12 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
     ms = _check_members(members, per_ok=dev.type == "cuda", self_play_ok=self_play is not None)
     if episode_end not in ("max_steps", "done"):
         raise ValueError("episode_end must be 'max_steps' or 'done'")
-    if explore not in ("torch", "device"):
-        raise ValueError("explore must be 'torch' or 'device'")
-    if collect not in ("torch", "device"):
-        raise ValueError("collect must be 'torch' or 'device'")
+    check_collect_args(explore, collect, self_play == "step", on_step)
     if eval_fn is not None and evaluator is not None:
         raise ValueError("pass eval_fn (one call per member) or evaluator (one call per evaluation), not both")
-    if collect == "device":
-        if explore != "device":
-            raise ValueError("collect='device' runs behind hkl_explore: it needs explore='device'")
-        if self_play == "step":
-            raise ValueError("collect='device' draws a snapshot per arena and step: self_play='step' sampling is not "
-                             "supported on the device, pass self_play='arena'")
-        if on_step is not None:
-            raise ValueError("collect='device' stores the transitions on the device without materialising a step's "
-                             "rows: on_step is not supported")
     S, n = len(ms), int(n_arenas)
     N = S * n
-    c0 = ms[0][0]
+    c0, seeds = ms[0][0], [s for _, s, _ in ms]
     planned = rounds * c0.max_steps * n
     agents = []
     for cfg, seed, resume in ms:
@@ -473,11 +439,11 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
                            seed=ms[0][1])
     if collect == "device" and self_play is None:  # the Collector's mix, with no member keeping a pool
         mix = PopulationOpponentMix([dataclasses.replace(c, use_self_play=False) for c, _, _ in ms],
-                                    [s for _, s, _ in ms], n, dev, sampling="arena")
+                                    seeds, n, dev, sampling="arena")
     elif self_play is None:
         mix = OpponentMix(N, c0.curriculum_name, False, c0.self_play_interval, c0.self_play_pool_size, dev, ms[0][1])
     else:
-        mix = PopulationOpponentMix([c for c, _, _ in ms], [s for _, s, _ in ms], n, dev, sampling=self_play)
+        mix = PopulationOpponentMix([c for c, _, _ in ms], seeds, n, dev, sampling=self_play)
     cap = replay_capacity or max(c0.buffer_size, n * c0.max_steps)
     if any(c.prioritized_replay for c, _, _ in ms):
         ring = PopulationPrioritizedRing(S, cap, prioritized=[c.prioritized_replay for c, _, _ in ms],
@@ -490,33 +456,29 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
     bank = PolicyBank(S, dev)
     for j, ag in enumerate(agents):
         bank.replace(j, ag.actor)
-    member_of = torch.arange(N, device=dev) // n  # [N] int64
-    policy = member_of.to(torch.int32)
-    local = (torch.arange(N, device=dev) % n).to(torch.float64)  # an arena's index inside its member
-    # one generator per noise mode over that mode's arenas (unit scale: the arena's own scale multiplies the draw)
-    modes = {}
-    for j, (cfg, seed, _) in enumerate(ms):
-        modes.setdefault(cfg.noise_mode, []).append(j)
-    gens = {}
-    for mname, js in modes.items():
-        rows = torch.cat([torch.arange(j * n, (j + 1) * n, device=dev) for j in js])
-        gens[mname] = (make_noise(mname, rows.numel(), 4, 1.0, c0.max_steps, dev, ms[js[0]][1]), rows, js)
-    start_t = torch.tensor([float(c.start_steps) for c, _, _ in ms], dtype=torch.float64, device=dev)
-    explorer = None
+    # on a GPU the kernels, and an error without the library: no quiet fall-back to the numpy laws
+    backend = "hip" if dev.type == "cuda" else "torch"
     if explore == "device":
-        from .explore import Explorer, Member, sync_agents
+        from .explore import Explorer, Member
 
-        # on a GPU the kernel, and an error without the library: no quiet fall-back to the numpy law
-        explorer = Explorer(bank, [Member.from_agent(ag) for ag in agents], n, policy=policy,
-                            backend="hip" if dev.type == "cuda" else "torch")
-    collector = None
+        explorer = Explorer(bank, [Member.from_agent(ag) for ag in agents], n,
+                            policy=(torch.arange(N, device=dev) // n).to(torch.int32), backend=backend)
+    else:
+        explorer = PopulationExplorer(agents, bank, n)
     if collect == "device":
         from .collect import Collector
 
-        collector = Collector(env, bank, mix, ring, explorer, [s for _, s, _ in ms], n,
-                              backend="hip" if dev.type == "cuda" else "torch", episode_end=episode_end,
+        collector = Collector(env, bank, mix, ring, explorer, seeds, n, backend=backend, episode_end=episode_end,
                               poll_every=poll_every)
-    act8 = torch.zeros((N, 8), device=dev)
+    else:
+        store = None
+        if on_step is not None:
+            all_rows = torch.arange(N, device=dev)
+
+            def store(rows, res, *row):  # the collector's own ragged push, shown to the hook
+                on_step(collector.push(rows, res, *row), all_rows if rows is None else rows, *row, res)
+
+        collector = TorchCollector(env, bank, mix, ring, explorer, seeds, n, episode_end=episode_end, store=store)
     stats = [{"env_steps": 0, "updates": 0, "updates_per_round": updates, "batch": batch,
               "replay_ratio": updates * batch / (n * c0.max_steps), "replay_capacity": cap, "critic_loss": [],
               "actor_loss": [], "mean_reward": [], "opponents": [], "evals": [], "round_time": [],
@@ -525,86 +487,18 @@ def train_population(members, n_arenas=20, rounds=10, device="cuda:0", mode=Mode
         for st in stats:
             st["pool_size"] = []
     episodes = 0
-    stop_at_done = episode_end == "done"
     clock = RoundClock(dev, timing, c0.eval_interval)
-    all_rows = torch.arange(N, device=dev)
-
-    def store(rows, res, *row):  # ragged over the members
-        m = member_of if rows is None else member_of[rows]
-        ring.push(m, *row)
-        if on_step is not None:
-            on_step(m, all_rows if rows is None else rows, *row, res)
-
     for rnd in range(rounds):
         clock.start()
         mix.update_schedule((episodes + 1) / (rounds * n))
-        obs, obs2 = reset_round(env, "seeded", mode, rnd, n, [seed for _, seed, _ in ms])
-        if explorer is None:
-            for g, _, _ in gens.values():
-                g.reset()
-        else:
-            explorer.reset_noise()
-        count_t = None  # explore="device", episode_end="done": the members' running arenas, kept on the device
-        ep_reward = torch.zeros(N, device=dev)
-        alive = torch.ones(N, dtype=torch.bool, device=dev)
-        n_alive = [n] * S  # per member: the arenas whose episode is still running
-        round_steps = [0] * S
-        if collector is not None:  # the whole round on the device; the loop below is collect="torch"'s
-            collector.begin_round(obs, obs2, c0.max_steps)
-            collector.run_round()
-        for _ in range(c0.max_steps if collector is None else 0):
-            if explorer is None:
-                # ---- TD3.act per member: count, random phase, annealed scale (host scalars -> [S] tensors)
-                first = [ag.total_steps + 1 for ag in agents]
-                for ag, k in zip(agents, n_alive):
-                    ag.total_steps += k
-                all_random = [ag.total_steps < ag.cfg.start_steps for ag in agents]
-                for ag, rnd_phase in zip(agents, all_random):
-                    if not rnd_phase:
-                        ag.current_noise_scale = ag.noise_scale()
-                scale_t = torch.tensor([ag.current_noise_scale for ag in agents], dtype=torch.float32, device=dev)
-                first_t = torch.tensor(first, dtype=torch.float64, device=dev)
-                allr_t = torch.tensor(all_random, dtype=torch.bool, device=dev)
-                a = bank.act(obs, policy)
-                noise = torch.zeros((N, 4), device=dev)
-                for g, rows, js in gens.values():
-                    if not all(all_random[j] for j in js):
-                        noise[rows] = g().float()
-                a = torch.clamp(a + noise * scale_t[member_of][:, None], -1, 1)
-                if any(f < ag.cfg.start_steps for f, ag in zip(first, agents)):
-                    rnd_rows = allr_t[member_of] | ((local + first_t[member_of]) < start_t[member_of])
-                    a = torch.where(rnd_rows[:, None], torch.rand((N, 4), device=dev) * 2 - 1, a)
-            else:  # one call: the actions land in act8[:, :4]
-                a = explorer.explore(obs, act8, 0, count=count_t)[:, :4]
-            if self_play is None:
-                policy2, a2, _ = mix.select(obs2)
-                if a2 is not None:
-                    act8[:, 4:] = a2
-            else:  # the self-play arenas' actions go straight into act8[:, 4:8]
-                policy2, _, _ = mix.select(obs2, out=act8)
-            if explorer is None:
-                act8[:, :4] = a
-            res = env.step(act8, with_agent_two=True, policy2=policy2)
-            o2, r, d = res.obs.clone(), res.reward.clone(), res.done.clone()
-            for j in range(S):
-                round_steps[j] += n_alive[j]
-            store_step(store, mix, stop_at_done, alive, ep_reward, res, obs, a, r, o2, d)
-            if stop_at_done:
-                if explorer is not None:
-                    count_t = alive.view(S, n).sum(1, dtype=torch.int32)
-                n_alive = alive.view(S, n).sum(1).tolist()  # the step's one host sync, as train's
-                if not any(n_alive):
-                    break
-            obs, obs2 = o2, res.obs2.clone()
+        obs, obs2 = reset_round(env, "seeded", mode, rnd, n, seeds)
+        explorer.reset_noise()
+        collector.begin_round(obs, obs2, c0.max_steps)
+        collector.run_round()
         episodes += n
-        if explorer is not None:
-            sync_agents(explorer, agents)
-        if collector is not None:  # per member; the snapshots precede the updates
-            round_steps, ep_reward, opp = collector.end_round([ag.actor for ag in agents], n)
-        elif self_play is None:
-            opp = [mix.end_round()] * S  # the population's counts: one mix over all arenas
-        else:
-            opp = mix.end_round([ag.actor for ag in agents], n)  # per member; snapshots precede the updates
+        explorer.sync(agents)
+        # per member; the snapshots precede the updates
+        round_steps, ep_reward, opp = collector.end_round([ag.actor for ag in agents], n)
         mean_r = ep_reward.view(S, n).mean(1).tolist()
         for j in range(S):
             stats[j]["env_steps"] += round_steps[j]

@@ -34,14 +34,15 @@ the reference's replay ratio (samples drawn per stored transition, ``train_iters
 """
 import json
 import math
-import time
 from dataclasses import dataclass, fields
 
 import numpy as np
 import torch
 
 from .constants import Mode
-from .evaluate import Actor, reset_params
+from .evaluate import Actor
+from .host_round import (AgentExplorer, RoundClock, TorchCollector, check_collect_args, reset_round,  # noqa: F401
+                         store_step)
 from .noise import make_noise
 
 
@@ -626,74 +627,6 @@ class Learner(PairRunner):
         return (s[0] / s[2] if s[2] else None), (s[1] / s[3] if s[3] else None)
 
 
-def reset_round(env, reset, mode, rnd, n, seeds):
-    """(obs, obs2) after resetting ``env`` for round ``rnd`` of ``train`` / ``train_population``: one block of ``n``
-    arenas per entry of ``seeds``, whose arena i plays episode e = rnd * n + i + 1 of that seed's run, placed like
-    ``reset(seed=seed + e)`` with the puck side toggling per reset.  reset: "seeded" (drawn by the kernel where the
-    env has ``reset_seeded``, else on the host), "seeded_host", or "device" (the kernel's Philox placement)."""
-    if reset == "device":
-        pair = env.reset()
-    elif reset == "seeded" and hasattr(env, "reset_seeded"):
-        # the same episodes as below, drawn by the kernel: seeds and puck sides are reset_params' own
-        e = np.arange(rnd * n, (rnd + 1) * n, dtype=np.int64)
-        st = torch.cat([torch.arange(s + 1 + rnd * n, s + 1 + (rnd + 1) * n, device=env.device) for s in seeds])
-        pair = env.reset_seeded(st, one_starting=np.tile((e % 2) == 1, len(seeds)))
-    else:
-        env.reset_params(np.concatenate([reset_params(n, s + rnd * n + 1, mode, first_reset=rnd * n)[0]
-                                         for s in seeds]))
-        pair = env.observe()
-    return tuple(t.clone() for t in pair)
-
-
-def store_step(store, mix, stop_at_done, alive, ep_reward, res, obs, a, r, o2, d):
-    """A collection step's bookkeeping for both ``episode_end`` values: ``store(rows, res, obs, a, r, o2, d)`` gets
-    the transitions to keep (rows: their arena indices, or None for all arenas), ``mix`` the step's outcomes, and
-    ``ep_reward`` the rewards.  episode_end="done" keeps only the arenas still ``alive`` and clears the flag of those
-    that ended (in place); the caller counts the survivors."""
-    if stop_at_done:  # only the transitions of episodes that were still running are stored
-        idx = torch.nonzero(alive).squeeze(1)
-        store(idx, res, obs[idx], a[idx], r[idx], o2[idx], d[idx])
-        mix.register_outcomes(d & alive, r)
-        ep_reward += torch.where(alive, r, torch.zeros_like(r))
-        alive &= d == 0
-    else:
-        store(None, res, obs, a, r, o2, d)
-        mix.register_outcomes(d, r)
-        ep_reward += r
-
-
-class RoundClock:
-    """A training round's wall-clock marks (with ``timing``: a device synchronise before each) and the evaluation
-    schedule, every ``eval_interval`` episodes."""
-
-    def __init__(self, device, timing, eval_interval):
-        self.device, self.timing, self.interval, self.next_eval = device, timing, eval_interval, eval_interval
-
-    def mark(self):
-        if self.timing:
-            torch.cuda.synchronize(self.device)
-        return time.perf_counter()
-
-    def start(self):
-        self.t0 = self.mark()
-
-    def collected(self):
-        self.t1 = self.mark()
-
-    def updated(self, stats):
-        """Append (collection seconds, update seconds) to every dict's "round_time" (with ``timing``)."""
-        t2 = self.mark()
-        if self.timing:
-            for st in stats:
-                st["round_time"].append((self.t1 - self.t0, t2 - self.t1))
-
-    def eval_due(self, episodes):
-        due = episodes >= self.next_eval
-        if due:
-            self.next_eval = (episodes // self.interval + 1) * self.interval
-        return due
-
-
 def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_per_round=None, mode=Mode.NORMAL,
           curriculum=None, use_self_play=None, self_play_interval=None, pool_size=None, reset="seeded", log=None,
           replay_capacity=None, graphs=True, eval_fn=None, learner_batch=None, timing=False, replay_ratio=None,
@@ -738,20 +671,12 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
     round's ``stats["opponents"]`` entry then also lists the arena-steps per snapshot.  mix: a ready OpponentMix
     for ``n_arenas`` on ``device`` to use instead of building one (a pool carried over from an earlier run).
 
-    explore: "torch" (default) acts through ``TD3.act``.  "device" acts through a ``hockey_amd.explore.Explorer`` on a
-    one-slot PolicyBank (refreshed after each round's updates): one ``hkl_explore`` call per step writes player 1's
-    action columns of the step kernel's input, the agent's step count and noise state live on the device, and
-    ``agent.total_steps`` / ``current_noise_scale`` are read back at the end of a round.  The law is ``TD3.act``'s; the
-    draws are Philox's, keyed by the agent's seed (hockey_amd.explore lists the batched differences).
-
-    collect: "torch" (default) is the loop described above.  "device" (needs explore="device") runs every step through a
-    one-member ``hockey_amd.collect.Collector``: ``hkl_explore``, ``hkl_opp_draw``, one ``PolicyBank.act`` for the
-    self-play arenas, the step kernel and ``hkl_collect``, with nothing read back per step (episode_end="done": the
-    survivors' count every ``poll_every`` steps; the results do not depend on it).  The ring is then a one-member
-    ``PopulationRing`` (prioritized replay: a ``PopulationPrioritizedRing``, which needs per_sampler="device" and the
-    fused learner) and the mix a one-member ``PopulationOpponentMix`` with a snapshot drawn per arena and step, so
-    ``self_play_sampling="step"``, a ready ``mix`` and ``on_step`` raise ValueError.  hockey_amd.collect lists the
-    batched differences from collect="torch"."""
+    explore / collect: "torch" (default) or "device": where exploration and the rest of a collection step run
+    (hockey_amd.host_round states both, with the collectors).  Here S = 1: explore="device" acts on a one-slot
+    PolicyBank; collect="device" makes the ring a one-member ``PopulationRing`` (prioritized replay: a
+    ``PopulationPrioritizedRing``, which needs per_sampler="device" and the fused learner) and the mix a one-member
+    ``PopulationOpponentMix`` with a snapshot drawn per arena and step, so ``self_play_sampling="step"``, a ready ``mix``
+    and ``on_step`` raise ValueError.  poll_every: collect="device"'s steps between two reads of the survivors' count."""
     from .opponents import OpponentMix
     from .vec_env import VecHockeyEnv
 
@@ -760,22 +685,13 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
         raise ValueError("per_sampler must be 'torch' or 'device'")
     if reset not in ("seeded", "seeded_host", "device"):
         raise ValueError("reset must be 'seeded', 'seeded_host' or 'device'")
-    if explore not in ("torch", "device"):
-        raise ValueError("explore must be 'torch' or 'device'")
-    if collect not in ("torch", "device"):
-        raise ValueError("collect must be 'torch' or 'device'")
+    if episode_end not in ("max_steps", "done"):
+        raise ValueError("episode_end must be 'max_steps' or 'done'")
+    check_collect_args(explore, collect, self_play_sampling == "step", on_step)
     if collect == "device":
-        if explore != "device":
-            raise ValueError("collect='device' runs behind hkl_explore: it needs explore='device'")
-        if self_play_sampling == "step":
-            raise ValueError("collect='device' draws a snapshot per arena and step: self_play_sampling='step' is not "
-                             "supported on the device")
         if mix is not None:
             raise ValueError("collect='device' builds its own one-member PopulationOpponentMix: a ready mix is not "
                              "supported")
-        if on_step is not None:
-            raise ValueError("collect='device' stores the transitions on the device without materialising a step's "
-                             "rows: on_step is not supported")
         if cfg.prioritized_replay and per_sampler != "device":
             raise ValueError("collect='device' pushes priorities through hkl_per_push_group: prioritized replay needs "
                              "per_sampler='device'")
@@ -804,7 +720,6 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
                           sampling=self_play_sampling or "step")
     elif self_play_sampling is not None and mix.sampling != self_play_sampling:
         raise ValueError(f"mix samples per {mix.sampling}, self_play_sampling asks for {self_play_sampling}")
-    per_arena = mix.sampling == "arena"
     cap = replay_capacity or max(cfg.buffer_size, n_arenas * cfg.max_steps)
     per_ring = DevicePrioritizedRing if per_sampler == "device" else PrioritizedRing
     pop_ring = None
@@ -823,91 +738,52 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
         raise ValueError("collect='device' with prioritized replay samples through the fused learner only")
     updates = updates_per_round if updates_per_round is not None else \
         updates_for(cfg, n_arenas, cfg.max_steps, batch, replay_ratio)
-    act8 = torch.zeros((n_arenas, 8), device=device)
     stats = {"env_steps": 0, "updates": 0, "updates_per_round": updates, "batch": batch,
              "replay_ratio": updates * batch / (n_arenas * cfg.max_steps),
              "replay_capacity": cap, "critic_loss": [], "actor_loss": [], "mean_reward": [], "opponents": [],
              "pool_size": [], "evals": [], "round_time": []}
     episodes = 0
-    if episode_end not in ("max_steps", "done"):
-        raise ValueError("episode_end must be 'max_steps' or 'done'")
-    stop_at_done = episode_end == "done"
     clock = RoundClock(device, timing, cfg.eval_interval)
-    explorer = None
+    # on a GPU the kernels, and an error without the library: no quiet fall-back to the numpy laws
+    backend = "hip" if agent.device.type == "cuda" else "torch"
+    bank = None
     if explore == "device":
-        from .explore import Explorer, Member, sync_agents
+        from .explore import Explorer, Member
         from .policy_bank import PolicyBank
 
         bank = PolicyBank(1, agent.device)
         bank.replace(0, agent.actor)
-        # on a GPU the kernel, and an error without the library: no quiet fall-back to the numpy law
-        explorer = Explorer(bank, [Member.from_agent(agent)], n_arenas,
-                            backend="hip" if agent.device.type == "cuda" else "torch")
-
-    collector = None
-    if collect == "device":
-        from .collect import Collector
-
-        collector = Collector(env, bank, mix, pop_ring, explorer, [seed], n_arenas,
-                              backend="hip" if agent.device.type == "cuda" else "torch", episode_end=episode_end,
-                              poll_every=poll_every)
+        explorer = Explorer(bank, [Member.from_agent(agent)], n_arenas, backend=backend)
+    else:
+        explorer = AgentExplorer(agent)
 
     def store(rows, res, *row):
         ring.push(*row)
         if on_step is not None:
             on_step(*row, res)
 
+    if collect == "device":
+        from .collect import Collector
+
+        collector = Collector(env, bank, mix, pop_ring, explorer, [seed], n_arenas, backend=backend,
+                              episode_end=episode_end, poll_every=poll_every)
+    else:
+        collector = TorchCollector(env, bank, mix, ring, explorer, [seed], n_arenas, episode_end=episode_end,
+                                   store=store)
     for rnd in range(rounds):
         clock.start()
         mix.update_schedule((episodes + 1) / (rounds * n_arenas))  # update_schedule(ep, max_episodes)
         obs, obs2 = reset_round(env, reset, mode, rnd, n_arenas, [seed])
-        if explorer is None:
-            agent.reset_noise()
-        else:
-            explorer.reset_noise()
-        ep_reward = torch.zeros(n_arenas, device=device)
-        alive = torch.ones(n_arenas, dtype=torch.bool, device=device)  # episode_end="done": not yet done
-        n_alive, round_steps = n_arenas, 0
-        count_t = None  # explore="device", episode_end="done": the running arenas, kept on the device
-        if collector is not None:  # the whole round on the device; the loop below is collect="torch"'s
-            collector.begin_round(obs, obs2, cfg.max_steps)
-            collector.run_round()
-        for _ in range(cfg.max_steps if collector is None else 0):
-            if explorer is None:
-                a = agent.act(obs, count=n_alive)
-            else:  # lands in act8[:, :4] directly
-                a = explorer.explore(obs, act8, 0, count=count_t)[:, :4]
-            if per_arena:  # the self-play arenas' actions land in act8[:, 4:8] directly
-                policy2, _, _ = mix.select(obs2, out=act8)
-                a2 = None
-            else:
-                policy2, a2, _ = mix.select(obs2)
-            if explorer is None:
-                act8[:, :4] = a
-            if a2 is not None:
-                act8[:, 4:] = a2
-            res = env.step(act8, with_agent_two=True, policy2=policy2)
-            o2, r, d = res.obs.clone(), res.reward.clone(), res.done.clone()
-            round_steps += n_alive
-            store_step(store, mix, stop_at_done, alive, ep_reward, res, obs, a, r, o2, d)
-            if stop_at_done:
-                if explorer is not None:
-                    count_t = alive.sum(dtype=torch.int32).reshape(1)
-                n_alive = int(alive.sum())
-                if n_alive == 0:
-                    break
-            obs, obs2 = o2, res.obs2.clone()
+        explorer.reset_noise()
+        collector.begin_round(obs, obs2, cfg.max_steps)
+        collector.run_round()
         episodes += n_arenas
-        if explorer is not None:
-            sync_agents(explorer, [agent])
-        if collector is not None:
-            (round_steps,), ep_reward, (opp,) = collector.end_round([agent.actor], n_arenas)
-        else:
-            opp = mix.end_round(agent.actor, episodes=n_arenas)
+        explorer.sync([agent])
+        (round_steps,), ep_reward, (opp,) = collector.end_round([agent.actor], n_arenas)
         stats["env_steps"] += round_steps
         stats["mean_reward"].append(float(ep_reward.mean().item()))
         stats["opponents"].append(opp)
-        stats["pool_size"].append(mix.pool_sizes()[0] if collector is not None else
+        stats["pool_size"].append(mix.pool_sizes()[0] if collect == "device" else
                                   len(mix.pool) if mix.pool is not None else 0)
         clock.collected()
         if agent.total_steps > batch:  # _train_agent's guard (train.py:177-185)
@@ -917,7 +793,7 @@ def train(n_arenas=1024, rounds=10, cfg=None, device="cuda:0", seed=0, updates_p
             stats["critic_loss"].append(cl)
             if al is not None:
                 stats["actor_loss"].append(al)
-            if explorer is not None:  # the actor changed: refresh the acting bank
+            if bank is not None:  # the actor changed: refresh the acting bank
                 bank.replace(0, agent.actor)
         clock.updated([stats])
         if eval_fn is not None and clock.eval_due(episodes):

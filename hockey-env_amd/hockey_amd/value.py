@@ -24,7 +24,7 @@ import torch
 
 from . import _native
 from .learner_hip import PACK_FLOATS, Net, ValueIO, check, lib, ptr, stream_ptr
-from .policy_bank import _hip_ready
+from .policy_bank import _hip_ready, resolve_backend
 
 _LAYERS = ("fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias", "fc3.weight", "fc3.bias")
 
@@ -135,13 +135,6 @@ class ValueFn:
             t = t.contiguous()
         return t
 
-    def _backend(self, backend):
-        if backend not in ("auto", "hip", "torch"):
-            raise ValueError("backend must be 'auto', 'hip' or 'torch'")
-        if backend == "auto":
-            backend = "hip" if _hip_ready(self.device) else "torch"
-        return backend
-
     # ------------------------------------------------------------------ hip
     def _hip(self, obs, act, q1=False, q2=False, qmin=False, act_out=False):
         """One hkl_value call; returns the requested outputs (None for the others) as (q1, q2, qmin, act_out)."""
@@ -183,7 +176,7 @@ class ValueFn:
         """(q1, q2), [n] each: both critics on ``obs`` ([n, >= 18] float32, the first 18 columns are the
         observation) and ``act`` ([n, >= 4] float32, the first 4 columns an action in the env's range).  Both need
         unit column stride; their row strides are passed on (views such as ``act8[:, :4]`` are read in place)."""
-        backend = self._backend(backend)
+        backend = resolve_backend(backend, self.device)
         obs = self._rows(obs, "obs", 18)
         act = self._rows(act, "act", 4, obs.shape[0])
         if backend == "torch":
@@ -193,7 +186,7 @@ class ValueFn:
     @torch.no_grad()
     def qmin(self, obs, act, backend="auto"):
         """min(q1, q2) of ``q`` [n]."""
-        backend = self._backend(backend)
+        backend = resolve_backend(backend, self.device)
         obs = self._rows(obs, "obs", 18)
         act = self._rows(act, "act", 4, obs.shape[0])
         if backend == "torch":
@@ -203,7 +196,7 @@ class ValueFn:
     @torch.no_grad()
     def v(self, obs, backend="auto", return_action=False):
         """V(s) = min(Q1, Q2)(s, actor(s)) [n]; with return_action also the actor's action [n, 4]."""
-        backend = self._backend(backend)
+        backend = resolve_backend(backend, self.device)
         obs = self._rows(obs, "obs", 18)
         if backend == "torch":
             a = self._act_torch(obs)

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Exploration acting on the device (hockey_amd.explore, one hkl_explore call per step) against the acting path it
 replaces, which survives unchanged as explore="torch": ``TD3.act`` in ``train`` and its per-member restatement in
-``train_population`` (host arithmetic, three uploads, ``hkl_act``, the noise generators, multiply / add / clamp, the
-random-phase mask, the copy into the step kernel's action columns).
+``train_population`` (hockey_amd.host_round's two host explorers: host arithmetic, three uploads, ``hkl_act``, the
+noise generators, multiply / add / clamp, the random-phase mask, the copy into the step kernel's action columns).
 
 Three measurements, device against torch, in ONE process and one session:
   step        ms per acting step at S x 20 arenas for S in --sizes (the four noise modes in turn over the members,
@@ -31,7 +31,7 @@ sys.path.insert(0, os.path.join(ROOT, "hockey-env_amd"))
 import torch  # noqa: E402
 
 from hockey_amd.explore import Explorer, Member  # noqa: E402
-from hockey_amd.noise import make_noise  # noqa: E402
+from hockey_amd.host_round import AgentExplorer, PopulationExplorer  # noqa: E402
 from hockey_amd.policy_bank import PolicyBank  # noqa: E402
 from hockey_amd.population import train_population  # noqa: E402
 from hockey_amd.td3 import TD3, TD3Config, train  # noqa: E402
@@ -64,8 +64,8 @@ def _alternate(legs, steps, repeats, warmup):
 
 
 def population_step(S, n, steps, repeats, warmup):
-    """One acting step of train_population at S x n arenas: its explore="torch" block, restated line for line on the
-    same objects, against Explorer.explore."""
+    """One acting step of train_population at S x n arenas: its explore="torch" explorer
+    (hockey_amd.host_round.PopulationExplorer) against Explorer.explore, on the same bank."""
     dev, N = torch.device(DEV), S * n
     cfgs = [TD3Config(noise_mode=NOISES[j % 4], max_steps=250) for j in range(S)]
     agents = [TD3(c, dev, 100 + j, max_total_steps=10_000 * 250 * n, n_envs=1) for j, c in enumerate(cfgs)]
@@ -73,52 +73,21 @@ def population_step(S, n, steps, repeats, warmup):
         ag.total_steps = PAST
     bank = PolicyBank(S, dev)
     bank.replace_many(range(S), [ag.actor for ag in agents])
-    member_of = torch.arange(N, device=dev) // n
-    policy = member_of.to(torch.int32)
-    local = (torch.arange(N, device=dev) % n).to(torch.float64)
-    modes = {}
-    for j, c in enumerate(cfgs):
-        modes.setdefault(c.noise_mode, []).append(j)
-    gens = {}
-    for mname, js in modes.items():
-        rows = torch.cat([torch.arange(j * n, (j + 1) * n, device=dev) for j in js])
-        gens[mname] = (make_noise(mname, rows.numel(), 4, 1.0, 250, dev, 100 + js[0]), rows, js)
-    start_t = torch.tensor([float(c.start_steps) for c in cfgs], dtype=torch.float64, device=dev)
+    policy = (torch.arange(N, device=dev) // n).to(torch.int32)
     act8 = torch.zeros((N, 8), device=dev)
     obs = torch.randn(N, 18, device=dev)
-    n_alive = [n] * S
-
-    def torch_step():  # hockey_amd.population.train_population, explore="torch"
-        first = [ag.total_steps + 1 for ag in agents]
-        for ag, k in zip(agents, n_alive):
-            ag.total_steps += k
-        all_random = [ag.total_steps < ag.cfg.start_steps for ag in agents]
-        for ag, rnd_phase in zip(agents, all_random):
-            if not rnd_phase:
-                ag.current_noise_scale = ag.noise_scale()
-        scale_t = torch.tensor([ag.current_noise_scale for ag in agents], dtype=torch.float32, device=dev)
-        first_t = torch.tensor(first, dtype=torch.float64, device=dev)
-        allr_t = torch.tensor(all_random, dtype=torch.bool, device=dev)
-        a = bank.act(obs, policy)
-        noise = torch.zeros((N, 4), device=dev)
-        for g, rows, js in gens.values():
-            if not all(all_random[j] for j in js):
-                noise[rows] = g().float()
-        a = torch.clamp(a + noise * scale_t[member_of][:, None], -1, 1)
-        if any(f < ag.cfg.start_steps for f, ag in zip(first, agents)):
-            rnd_rows = allr_t[member_of] | ((local + first_t[member_of]) < start_t[member_of])
-            a = torch.where(rnd_rows[:, None], torch.rand((N, 4), device=dev) * 2 - 1, a)
-        act8[:, :4] = a
-
+    host = PopulationExplorer(agents, bank, n)
     ex = Explorer(bank, [Member.from_agent(ag) for ag in agents], n, policy=policy)
     ex.total.fill_(PAST)
     rec = {"members": S, "arenas_per_member": n, "rows": N, "steps_per_timing": steps}
-    rec.update(_alternate({"torch": torch_step, "device": lambda: ex.explore(obs, act8, 0)}, steps, repeats, warmup))
+    rec.update(_alternate({"torch": lambda: host.explore(obs, act8, 0), "device": lambda: ex.explore(obs, act8, 0)},
+                          steps, repeats, warmup))
     return rec
 
 
 def wide_step(rows, steps, repeats, warmup):
-    """One acting step of train at ``rows`` arenas, one policy: TD3.act and the copy, against Explorer.explore."""
+    """One acting step of train at ``rows`` arenas, one policy: its explore="torch" explorer
+    (hockey_amd.host_round.AgentExplorer: TD3.act and the copy) against Explorer.explore."""
     dev = torch.device(DEV)
     agent = TD3(TD3Config(), dev, 3, max_total_steps=10 ** 12, n_envs=rows)
     agent.total_steps = PAST
@@ -128,22 +97,23 @@ def wide_step(rows, steps, repeats, warmup):
     ex.total.fill_(PAST)
     act8 = torch.zeros((rows, 8), device=dev)
     obs = torch.randn(rows, 18, device=dev)
-
-    def torch_step():  # hockey_amd.td3.train, explore="torch"
-        act8[:, :4] = agent.act(obs, count=rows)
-
+    host = AgentExplorer(agent)
     rec = {"rows": rows, "policies": 1, "steps_per_timing": steps}
-    rec.update(_alternate({"torch": torch_step, "device": lambda: ex.explore(obs, act8, 0)}, steps, repeats, warmup))
+    rec.update(_alternate({"torch": lambda: host.explore(obs, act8, 0), "device": lambda: ex.explore(obs, act8, 0)},
+                          steps, repeats, warmup))
     return rec
 
 
-def population_round(S, arenas=20):
+LEGS = {"torch": {"explore": "torch"}, "device": {"explore": "device"}}  # a round leg's training arguments
+
+
+def population_round(S, arenas=20, legs=LEGS):
     cfgs = [TD3Config(max_steps=250, use_self_play=False, curriculum_name="noise_study", noise_mode=NOISES[j % 4])
             for j in range(S)]
     rec = {"members": S, "arenas_per_member": arenas, "steps": 250}
-    for leg in ("torch", "device"):
+    for leg, kw in legs.items():
         _, st = train_population([(c, 100 + j) for j, c in enumerate(cfgs)], n_arenas=arenas, rounds=2, device=DEV,
-                                 timing=True, explore=leg)
+                                 timing=True, **kw)
         c, u = st[0]["round_time"][1]
         rec[leg + "_round_s"] = {"collect": c, "update": u, "total": c + u}
         rec["updates_per_round"] = st[0]["updates_per_round"]
@@ -152,12 +122,11 @@ def population_round(S, arenas=20):
     return rec
 
 
-def train_round(arenas):
+def train_round(arenas, legs=LEGS):
     cfg = TD3Config(use_self_play=False, curriculum_name="stage1")
     rec = {"arenas": arenas, "steps": cfg.max_steps, "what": "train(): the second round's collection"}
-    for leg in ("torch", "device"):
-        _, st = train(n_arenas=arenas, rounds=2, cfg=cfg, device=DEV, seed=5, timing=True, updates_per_round=2,
-                      explore=leg)
+    for leg, kw in legs.items():
+        _, st = train(n_arenas=arenas, rounds=2, cfg=cfg, device=DEV, seed=5, timing=True, updates_per_round=2, **kw)
         c, u = st["round_time"][1]
         rec[leg + "_collect_s"] = c
         rec[leg + "_env_steps_per_s"] = arenas * cfg.max_steps / c
