@@ -1,12 +1,15 @@
 """Shared cases of tests/test_arena_copy.py (host build) and tests/test_gpu_arena_copy.py (GPU): the composed zoo
-batch with the oracle's uninterrupted run, the fork case and the lookahead case.  TEST INFRASTRUCTURE ONLY.
+batch with the oracle's uninterrupted run, the interrupted run, the fork case and the lookahead case, each over an
+implementation of tests/scene_lockstep.py.  TEST INFRASTRUCTURE ONLY.
 """
 import numpy as np
 import pytest
 
 import wave_zoo as W
+from hockey_amd import _native as N
+from scene_lockstep import STEP_FIELDS, check_step, oracle_run, run_batch
+from vec_lockstep import first_mismatch
 
-FIELDS = ("obs", "obs2", "reward", "reward2", "done", "info", "info2")
 N_ARENAS = 101  # one full wave and one of 37 lanes
 
 
@@ -26,15 +29,86 @@ def scen():
 @pytest.fixture(scope="module")
 def want(oracle, scen):
     """The oracle's uninterrupted 4 steps of the composed batch, and its final state."""
-    ov = oracle.OracleVec(N_ARENAS, policies=("external", "external"), auto_reset=False)
-    ov.set_state(scen["state"], scen["aux"])
-    steps = [ov.step(scen["actions"][t], with_agent_two=True) for t in range(W.K)]
-    out = {"steps": steps, "state": ov.get_state()}
+    return oracle_run(oracle, scen["state"], scen["aux"], scen["actions"])
+
+
+def state_equal(env, want_state):
+    """Per arena: the state words and aux rows equal want_state's."""
+    st, aux = env.get_state()
+    return (st.view(np.uint32) == want_state[0].view(np.uint32)).all(1) & (aux == want_state[1]).all(1)
+
+
+def no_bad_index(*envs):
+    for e in envs:
+        c = e.counters()
+        assert c[N.CNT_BAD_INDEX] == 0 and c[N.CNT_OVERFLOW] == 0
+
+
+def _rows_equal(got, want, rows, want_rows):
+    return all((got[f][rows].reshape(len(rows), -1).view(np.uint8)
+                == want[f][want_rows].reshape(len(rows), -1).view(np.uint8)).all() for f in STEP_FIELDS)
+
+
+def interrupted(env, scen, want, path, save, load):
+    """env (the scenarios in place): 2 steps in lockstep with the oracle, save(env), every arena reset and stepped,
+    load(env, saved), 2 more steps.  Returns per arena whether every output of steps 2..3 and the final state equal
+    the oracle's; closes env."""
+    for t, got in enumerate(run_batch(env, scen["actions"][:2], path)):
+        check_step(t, got, want["steps"][t], path)
+    saved = save(env)
+    env.reset()  # a device-placement reset, then one step of it: every arena overwritten
+    env.step(np.zeros((env.n, 8), np.float32))
+    assert not state_equal(env, want["state"]).any()
+    load(env, saved)
+    ok = np.ones(env.n, bool)
+    for t, got in enumerate(run_batch(env, scen["actions"][2:], path), start=2):
+        for f in STEP_FIELDS:
+            g, w = got[f].reshape(env.n, -1), want["steps"][t][f].reshape(env.n, -1)
+            ok &= (g.view(np.uint8) == w.view(np.uint8)).all(1)
+    ok &= state_equal(env, want["state"])
+    no_bad_index(env)
+    env.close()
+    return ok
+
+
+def fork_follows_the_oracle(oracle, env, path, fork):
+    """env (128 arenas): arenas 64..127 live another history for 3 steps, then fork(env, src, dst) gives them arenas
+    0..63 through a permuted destination list; from there all 128 arenas equal the oracle, whose arenas 64..127 lived
+    0..63's history from the reset.  Then one source arena into 37 destinations.  Closes env."""
+    params, max_t, actions, other = fork_case()
+    ov = oracle.OracleVec(128, policies=("external", "external"), auto_reset=False)
+    ov.reset(params=params, max_t=max_t)
+    env.reset_params(params, max_t=max_t)
+    pre = actions[:3].copy()
+    pre[:, 64:] = other
+    got = run_batch(env, pre, path)
+    touched, first = 0, np.arange(64)
+    for t in range(3):
+        w = ov.step(actions[t], with_agent_two=True)
+        assert _rows_equal(got[t], w, first, first), t
+        touched += int((w["info"][:, 2] != 0).sum())
+    assert touched > 0, "the case holds player-puck contacts"
+    assert not state_equal(env, ov.get_state())[64:].all()
+    perm = np.random.default_rng(7).permutation(64)
+    fork(env, perm, 64 + perm)
+    assert state_equal(env, ov.get_state()).all()
+    got = run_batch(env, actions[3:6], path)
+    for t in range(3, 6):
+        bad = first_mismatch(t, got[t - 3], ov.step(actions[t], with_agent_two=True), fields=STEP_FIELDS)
+        assert bad is None, bad
+    assert state_equal(env, ov.get_state()).all()
+    # K-way replication: arena 5 into 37 destinations, which then take arena 5's action
+    dst = np.arange(70, 107)
+    fork(env, np.full(37, 5), dst)
+    a = np.random.default_rng(8).uniform(-1, 1, (128, 8)).astype(np.float32)
+    a[dst] = a[5]
+    w = ov.step(a, with_agent_two=True)
+    assert _rows_equal(vars(env.step(a, with_agent_two=True)), w, dst, np.full(37, 5))
+    five = tuple(x[np.full(128, 5)] for x in ov.get_state())
+    assert state_equal(env, five)[dst].all()
+    no_bad_index(env)
+    env.close()
     ov.close()
-    for s in steps:
-        for v in s.values():
-            v.setflags(write=False)
-    return out
 
 
 def fork_case():
@@ -53,8 +127,6 @@ def fork_case():
     actions = np.concatenate([a, a], axis=1)
     other = rng.uniform(-1, 1, (3, 64, 8)).astype(np.float32)  # the host build's arenas 64..127 before the fork
     return params, np.full(128, 250, np.int32), actions, other
-
-
 
 
 def lookahead_case(oracle, M=5, K=8, H=6, n_live=8, hist=2):

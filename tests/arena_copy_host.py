@@ -10,9 +10,9 @@ import numpy as np
 import torch
 
 import hostcheck as H
+from hockey_amd import _native as N
 from hockey_amd import snapshot as S
 
-CNT_BAD_INDEX = 8
 _bound = False
 
 
@@ -75,4 +75,4 @@ def copy(dst, dst_idx, src, src_idx):
 
 
 def bad_index_count(hv):
-    return int(hv.counters()[CNT_BAD_INDEX])
+    return int(hv.counters()[N.CNT_BAD_INDEX])

@@ -64,7 +64,10 @@ POLICY = {"external": 0, "random": 1, "weak": 2, "strong": 3}
 
 
 class HostVec:
-    """Same call shapes as hockey_amd.vec_env.VecHockeyEnv for the calls the parity tests make (numpy)."""
+    """Same call shapes as hockey_amd.vec_env.VecHockeyEnv for the calls the parity tests make (numpy): the
+    implementation that tests/scene_lockstep.py's other views (GpuVec, OracleWorlds) are shaped after."""
+
+    paths = ("hk_step",)  # the launches it has: no hk_rollout
 
     def __init__(self, n, keep_mode=True, mode=0, auto_reset=False, vel_ref=False,
                  policies=("external", "external"), seed=0, arena_offset=0, diag_flags=0):

@@ -335,13 +335,15 @@ def check(m, full=True):
 
 
 def run(env, batch, aux=False):
-    """Drive any context with set_state / step(actions, debug) / get_state through the batch; numpy in and out.
-    aux=True: also the aux rows before / after each step (env.get_aux), as a third array."""
+    """Drive an implementation (the call shapes of tests/scene_lockstep.py) through the batch: (S[K + 1, N, 18],
+    D[K, N, 13]).  aux=True: also the aux rows before / after each step and each step's done flags, (S, D, A, done)."""
     env.set_state(batch.state, batch.aux)
-    S, D, A = [batch.state.copy()], [], [batch.aux.copy()]
+    S, D, A, done = [batch.state.copy()], [], [batch.aux.copy()], []
     for k in range(K):
-        D.append(env.step_debug(batch.actions[k]))
-        S.append(env.get_state())
-        if aux:
-            A.append(env.get_aux())
-    return (np.stack(S), np.stack(D), np.stack(A)) if aux else (np.stack(S), np.stack(D))
+        r = env.step(batch.actions[k], debug=True)
+        D.append(r.debug)
+        done.append(r.done)
+        st, ax = env.get_state()
+        S.append(st)
+        A.append(ax)
+    return (np.stack(S), np.stack(D), np.stack(A), np.stack(done)) if aux else (np.stack(S), np.stack(D))

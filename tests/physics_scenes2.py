@@ -627,5 +627,5 @@ def check(m):
 
 
 def run(env, batch):
-    """(S, D, A): physics_scenes.run with the aux rows as well."""
+    """(S, D, A, done): physics_scenes.run with the aux rows and the done flags as well."""
     return run_af(env, batch, aux=True)

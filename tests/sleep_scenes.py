@@ -493,18 +493,18 @@ def check(m, batch):
 
 
 def run(env, batch, first=0, last=K):
-    """Drive any context with set_state(state, aux, mask) / step_debug(actions) / get_state() through steps
-    first .. last - 1 of the batch (first = 0 puts the batch's state in place; a later first continues from the
-    context's own); numpy in and out.  Returns (S[last - first + 1, N, 18], D[last - first, N, 13])."""
+    """Drive an implementation (the call shapes of tests/scene_lockstep.py) through steps first .. last - 1 of the
+    batch (first = 0 puts the batch's state in place; a later first continues from the context's own).  Returns
+    (S[last - first + 1, N, 18], D[last - first, N, 13])."""
     if first == 0:
-        env.set_state(batch.state, batch.aux, None)
-    S, D = [np.array(batch.state) if first == 0 else env.get_state()], []
+        env.set_state(batch.state, batch.aux)
+    S, D = [np.array(batch.state) if first == 0 else env.get_state()[0]], []
     for k in range(first, last):
         if k == T0:
             patch = batch.twin_patch(S[-1])
             if patch is not None:
                 env.set_state(patch[0], None, patch[1])
-                S[-1] = env.get_state()
-        D.append(env.step_debug(batch.actions[k]))
-        S.append(env.get_state())
+                S[-1] = env.get_state()[0]
+        D.append(env.step(batch.actions[k], debug=True).debug)
+        S.append(env.get_state()[0])
     return np.stack(S), np.stack(D)

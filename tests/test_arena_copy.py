@@ -10,113 +10,43 @@ import pytest
 torch = pytest.importorskip("torch")
 
 import arena_copy_host as AC  # noqa: E402
-from arena_copy_cases import FIELDS, N_ARENAS, fork_case, scen, want  # noqa: E402,F401  (scen, want: fixtures)
+from arena_copy_cases import N_ARENAS, fork_follows_the_oracle, interrupted  # noqa: E402
+from arena_copy_cases import scen, want  # noqa: E402,F401  (module-scoped fixtures: the scenarios, the oracle's run)
 import hostcheck as H  # noqa: E402
-import wave_zoo as W  # noqa: E402
 from hockey_amd import _native as N  # noqa: E402
 from hockey_amd import snapshot as S  # noqa: E402
-from vec_lockstep import first_mismatch  # noqa: E402
-
-def _host(scen, n=N_ARENAS):
-    hv = H.HostVec(n, policies=("external", "external"), auto_reset=False)
-    hv.set_state(scen["state"][:n], scen["aux"][:n])
-    return hv
+from scene_lockstep import STEP_FIELDS, scene_env  # noqa: E402
 
 
-def _step(hv, scen, t):
+def _host(scen, n=N_ARENAS):  # noqa: F811
+    return scene_env(H.HostVec, scen["state"][:n], scen["aux"][:n])
+
+
+def _step(hv, scen, t):  # noqa: F811
     return vars(hv.step(scen["actions"][t][:hv.n], with_agent_two=True))
 
 
-def _state_equal(hv, want_state):
-    st, aux = hv.get_state()
-    return (st.view(np.uint32) == want_state[0].view(np.uint32)).all(1) & (aux == want_state[1]).all(1)
-
-
-def _garbage(hv):
-    """Overwrite every arena: a device-placement reset, then one step of it."""
-    hv.reset()
-    hv.step(np.zeros((hv.n, 8), np.float32))
-
-
-def _interrupted(scen, want, save, load):
-    """2 steps in lockstep with the oracle, save(hv), garbage, load(hv, saved), 2 more steps.  Returns per arena
-    whether every output of steps 2..3 and the final state equal the oracle's."""
-    hv = _host(scen)
-    for t in range(2):
-        bad = first_mismatch(t, _step(hv, scen, t), want["steps"][t], fields=FIELDS)
-        assert bad is None, bad
-    saved = save(hv)
-    _garbage(hv)
-    assert not _state_equal(hv, want["state"]).any()
-    load(hv, saved)
-    ok = np.ones(hv.n, bool)
-    for t in range(2, W.K):
-        got = _step(hv, scen, t)
-        for f in FIELDS:
-            g, w = got[f].reshape(hv.n, -1), want["steps"][t][f].reshape(hv.n, -1)
-            ok &= (g.view(np.uint8) == w.view(np.uint8)).all(1)
-    ok &= _state_equal(hv, want["state"])
-    assert AC.bad_index_count(hv) == 0
-    hv.close()
-    return ok
-
-
-def test_resume_from_snapshot_equals_uninterrupted_oracle(scen, want):
+def test_resume_from_snapshot_equals_uninterrupted_oracle(scen, want):  # noqa: F811
     """(1) snapshot -> every arena reset and stepped -> restore -> the oracle's uninterrupted trajectory."""
-    ok = _interrupted(scen, want, AC.snapshot, AC.restore)
+    ok = interrupted(_host(scen), scen, want, "hk_step", AC.snapshot, AC.restore)
     assert ok.all(), "arenas %s left the oracle's trajectory after restore" % np.nonzero(~ok)[0].tolist()
 
 
-def test_resume_from_get_state_is_not_exact(scen, want):
+def test_resume_from_get_state_is_not_exact(scen, want):  # noqa: F811
     """(2) the power of (1): the same interruption with get_state / set_state (the reference's 18 + 5 words) does
     NOT resume these scenarios exactly, so (1) passes because of what only the snapshot carries."""
-    ok = _interrupted(scen, want, lambda hv: hv.get_state(), lambda hv, s: hv.set_state(s[0], s[1]))
+    ok = interrupted(_host(scen), scen, want, "hk_step", lambda hv: hv.get_state(), lambda hv, s: hv.set_state(*s))
     assert not ok.all(), "set_state alone resumed every arena exactly: the scenarios show nothing"
 
 
 # ------------------------------------------------------------------------------------------------ fork
+def _fork(hv, src, dst):
+    assert AC.copy(hv, dst, hv, src) == 0
+
+
 def test_fork_to_other_indices_follows_the_oracle(oracle):
-    """(3) arenas 64..127 of the host build live another history for 3 steps, then take arenas 0..63 through a
-    permuted destination list; from there all 128 arenas equal the oracle, whose arenas 64..127 lived 0..63's
-    history from the reset.  Then one source arena into 37 destinations."""
-    params, max_t, actions, other = fork_case()
-    ov = oracle.OracleVec(128, policies=("external", "external"), auto_reset=False)
-    ov.reset(params=params, max_t=max_t)
-    hv = H.HostVec(128, policies=("external", "external"), auto_reset=False)
-    hv.reset_params(params, max_t=max_t)
-    touched = 0
-    for t in range(3):
-        w = ov.step(actions[t], with_agent_two=True)
-        a = actions[t].copy()
-        a[64:] = other[t]
-        g = vars(hv.step(a, with_agent_two=True))
-        assert first_mismatch(t, {f: g[f][:64] for f in FIELDS}, {f: w[f][:64] for f in FIELDS}, fields=FIELDS) is None
-        touched += int((w["info"][:, 2] != 0).sum())
-    assert touched > 0, "the case holds player-puck contacts"
-    assert not _state_equal(hv, ov.get_state())[64:].all()
-    perm = np.random.default_rng(7).permutation(64)
-    assert AC.copy(hv, 64 + perm, hv, perm) == 0
-    assert _state_equal(hv, ov.get_state()).all()
-    for t in range(3, 6):
-        w = ov.step(actions[t], with_agent_two=True)
-        bad = first_mismatch(t, vars(hv.step(actions[t], with_agent_two=True)), w, fields=FIELDS)
-        assert bad is None, bad
-    assert _state_equal(hv, ov.get_state()).all()
-    # K-way replication: arena 5 into 37 destinations, which then take arena 5's action
-    dst = np.arange(70, 107)
-    assert AC.copy(hv, dst, hv, np.full(37, 5)) == 0
-    a = np.random.default_rng(8).uniform(-1, 1, (128, 8)).astype(np.float32)
-    a[dst] = a[5]
-    w = ov.step(a, with_agent_two=True)
-    g = vars(hv.step(a, with_agent_two=True))
-    for f in FIELDS:
-        assert (g[f][dst].reshape(37, -1).view(np.uint8) == w[f][5].reshape(1, -1).view(np.uint8)).all(), f
-    st, aux = hv.get_state()
-    ost, oaux = ov.get_state()
-    assert (st[dst].view(np.uint32) == ost[5].view(np.uint32)).all() and (aux[dst] == oaux[5]).all()
-    assert AC.bad_index_count(hv) == 0
-    hv.close()
-    ov.close()
+    """(3) arena_copy_cases.fork_follows_the_oracle with hkh_copy_arenas as the fork."""
+    fork_follows_the_oracle(oracle, H.HostVec(128), "hk_step", _fork)
 
 
 # ------------------------------------------------------------------------------------------------ round trips, errors
@@ -150,7 +80,7 @@ def test_snapshot_save_load_restore_round_trip(played, scen, tmp_path, m):
     a = scen["actions"][2]
     g0 = vars(_step_twin(played, a))
     g1 = vars(other.step(a, with_agent_two=True))
-    for f in FIELDS:
+    for f in STEP_FIELDS:
         assert (g0[f][idx].reshape(m, -1).view(np.uint8) == g1[f][idx].reshape(m, -1).view(np.uint8)).all(), f
     assert AC.bad_index_count(other) == 0
     other.close()

@@ -10,21 +10,21 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 from hockey_amd import _native as N  # noqa: E402
-from arena_copy_cases import FIELDS, N_ARENAS, fork_case, lookahead_case  # noqa: E402
+from arena_copy_cases import N_ARENAS, fork_follows_the_oracle, interrupted, lookahead_case, no_bad_index  # noqa: E402
 from arena_copy_cases import scen, want  # noqa: E402,F401  (module-scoped fixtures: the scenarios, the oracle's run)
+from scene_lockstep import DEV, STEP_FIELDS, GpuVec, require_gfx950, run_batch, scene_env  # noqa: E402
 from vec_lockstep import first_mismatch  # noqa: E402
 
-DEV = "cuda:0"
 HK_E_INVALID = -1
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _gpu():
-    assert torch.cuda.is_available(), "GPU tests need the MI355X (gfx950)"
-    assert "gfx950" in torch.cuda.get_device_properties(0).gcnArchName
+    require_gfx950()
 
 
 def _vec(n, **kw):
+    """The VecHockeyEnv itself, for the tests of its torch-level calls."""
     from hockey_amd.vec_env import VecHockeyEnv
 
     kw.setdefault("policies", ("external", "external"))
@@ -35,108 +35,29 @@ def _t(a):
     return torch.as_tensor(a, device=DEV)
 
 
-def _np(res, t=None, fields=FIELDS):
-    return {f: (getattr(res, f) if t is None else getattr(res, f)[t]).detach().cpu().numpy() for f in fields}
-
-
-def _advance(env, actions, how):
-    """Steps with actions [k, n, 8] through k hk_step launches or one hk_rollout; returns the k output dicts."""
-    k = actions.shape[0]
-    if how == "step":
-        return [_np(env.step(_t(actions[t]), with_agent_two=True)) for t in range(k)]
-    ro = env.rollout(k, actions=_t(actions), with_agent_two=True)
-    return [_np(ro, t) for t in range(k)]
-
-
-def _state_equal(env, want_state):
-    st, aux = env.get_state()
-    st, aux = st.cpu().numpy(), aux.cpu().numpy()
-    return (st.view(np.uint32) == want_state[0].view(np.uint32)).all(1) & (aux == want_state[1]).all(1)
-
-
-def _no_bad_index(*envs):
-    for e in envs:
-        c = e.counters()
-        assert c[N.CNT_BAD_INDEX] == 0 and c[N.CNT_OVERFLOW] == 0
-
-
 def _zoo_env(scen):  # noqa: F811
-    env = _vec(N_ARENAS)
-    env.set_state(scen["state"], scen["aux"])
-    return env
-
-
-def _interrupted(scen, want, how, save, load):  # noqa: F811
-    env = _zoo_env(scen)
-    for t, got in enumerate(_advance(env, scen["actions"][:2], how)):
-        bad = first_mismatch(t, got, want["steps"][t], fields=FIELDS)
-        assert bad is None, bad
-    saved = save(env)
-    env.reset()
-    env.step(torch.zeros((env.n, 8), device=DEV))
-    assert not _state_equal(env, want["state"]).any()
-    load(env, saved)
-    ok = np.ones(env.n, bool)
-    for t, got in enumerate(_advance(env, scen["actions"][2:], how), start=2):
-        for f in FIELDS:
-            g, w = got[f].reshape(env.n, -1), want["steps"][t][f].reshape(env.n, -1)
-            ok &= (g.view(np.uint8) == w.view(np.uint8)).all(1)
-    ok &= _state_equal(env, want["state"])
-    _no_bad_index(env)
-    env.close()
-    return ok
+    """GpuVec with the scenarios in place; its .env is the VecHockeyEnv."""
+    return scene_env(GpuVec, scen["state"], scen["aux"])
 
 
 @pytest.mark.parametrize("how", ["step", "rollout"])
 def test_resume_from_snapshot_equals_uninterrupted_oracle(scen, want, how):  # noqa: F811
     """(5.1) snapshot -> every arena reset and stepped -> restore -> the oracle's uninterrupted trajectory."""
-    ok = _interrupted(scen, want, how, lambda e: e.snapshot(), lambda e, s: e.restore(s))
+    ok = interrupted(_zoo_env(scen), scen, want, "hk_" + how, lambda g: g.env.snapshot(),
+                     lambda g, s: g.env.restore(s))
     assert ok.all(), "arenas %s left the oracle's trajectory after restore" % np.nonzero(~ok)[0].tolist()
 
 
 def test_resume_from_get_state_is_not_exact(scen, want):  # noqa: F811
     """The power of (5.1) on the device: get_state / set_state alone does not resume these scenarios."""
-    ok = _interrupted(scen, want, "step", lambda e: tuple(x.clone() for x in e.get_state()),
-                      lambda e, s: e.set_state(s[0], s[1]))
+    ok = interrupted(_zoo_env(scen), scen, want, "hk_step", lambda g: g.get_state(), lambda g, s: g.set_state(*s))
     assert not ok.all()
 
 
 @pytest.mark.parametrize("how", ["step", "rollout"])
 def test_fork_to_other_indices_follows_the_oracle(oracle, how):
-    """(5.3) arenas 64..127 live another history for 3 steps, then take arenas 0..63 through a permuted destination
-    list; from there all 128 arenas equal the oracle.  Then one source arena into 37 destinations."""
-    params, max_t, actions, other = fork_case()
-    ov = oracle.OracleVec(128, policies=("external", "external"), auto_reset=False)
-    ov.reset(params=params, max_t=max_t)
-    env = _vec(128)
-    env.reset_params(params, max_t=max_t)
-    pre = actions[:3].copy()
-    pre[:, 64:] = other
-    got = _advance(env, pre, how)
-    for t in range(3):
-        w = ov.step(actions[t], with_agent_two=True)
-        assert first_mismatch(t, {f: got[t][f][:64] for f in FIELDS}, {f: w[f][:64] for f in FIELDS},
-                              fields=FIELDS) is None
-    assert not _state_equal(env, ov.get_state())[64:].all()
-    perm = np.random.default_rng(7).permutation(64)
-    env.fork(perm, 64 + perm)
-    assert _state_equal(env, ov.get_state()).all()
-    got = _advance(env, actions[3:6], how)
-    for t in range(3, 6):
-        bad = first_mismatch(t, got[t - 3], ov.step(actions[t], with_agent_two=True), fields=FIELDS)
-        assert bad is None, bad
-    assert _state_equal(env, ov.get_state()).all()
-    dst = np.arange(70, 107)
-    env.fork(np.full(37, 5), dst)
-    a = np.random.default_rng(8).uniform(-1, 1, (128, 8)).astype(np.float32)
-    a[dst] = a[5]
-    w = ov.step(a, with_agent_two=True)
-    g = _np(env.step(_t(a), with_agent_two=True))
-    for f in FIELDS:
-        assert (g[f][dst].reshape(37, -1).view(np.uint8) == w[f][5].reshape(1, -1).view(np.uint8)).all(), f
-    _no_bad_index(env)
-    env.close()
-    ov.close()
+    """(5.3) arena_copy_cases.fork_follows_the_oracle with VecHockeyEnv.fork (hk_copy_arenas) as the fork."""
+    fork_follows_the_oracle(oracle, GpuVec(128), "hk_" + how, lambda g, src, dst: g.env.fork(src, dst))
 
 
 def test_same_index_resume_with_device_draws(oracle):
@@ -150,15 +71,16 @@ def test_same_index_resume_with_device_draws(oracle):
     wantrun = [ov.step(with_agent_two=True, final_obs=True) for _ in range(40)]
     dones = np.stack([w["done"] for w in wantrun])
     assert dones[:20].any() and dones[20:].any(), "resets occur on both sides of the snapshot"
-    env = _vec(n, policies=("strong", "strong"), auto_reset=True, seed=seed)
+    g = GpuVec(n, policies=("strong", "strong"), auto_reset=True, seed=seed)
+    env = g.env
     mt_t = _t(mt)
     N.check(env.L.hk_reset(env._ctx, None, None, N.ptr(mt_t), None, env._stream()), "hk_reset")
-    fields = FIELDS + ("final_obs",)
+    fields = STEP_FIELDS + ("final_obs",)
 
     def run(t0):
         out = []
         for t in range(t0, t0 + 20):
-            got = _np(env.step(None, with_agent_two=True, final_obs=True), fields=fields)
+            got = vars(g.step(None, with_agent_two=True, final_obs=True))
             bad = first_mismatch(t, got, wantrun[t], fields=fields)
             assert bad is None, bad
             out.append(got)
@@ -167,36 +89,36 @@ def test_same_index_resume_with_device_draws(oracle):
     run(0)
     snap = env.snapshot()
     first = run(20)
-    end_state = [x.clone() for x in env.get_state()]
+    end_state = g.get_state()
     env.restore(snap)
     second = run(20)
     for a, b in zip(first, second):
         for f in fields:
             assert np.array_equal(a[f].view(np.uint8), b[f].view(np.uint8)), f
-    st, aux = env.get_state()
-    assert torch.equal(st.view(torch.int32), end_state[0].view(torch.int32)) and torch.equal(aux, end_state[1])
-    _no_bad_index(env)
-    env.close()
+    st, aux = g.get_state()
+    assert np.array_equal(st.view(np.uint32), end_state[0].view(np.uint32)) and np.array_equal(aux, end_state[1])
+    no_bad_index(g)
+    g.close()
     ov.close()
 
 
 def test_lift_one_arena_into_a_one_arena_context(scen):  # noqa: F811
     """(7) arena 77 of a 101-arena context, lifted into a one-arena context, steps like its source."""
     env = _zoo_env(scen)
-    _advance(env, scen["actions"][:2], "step")
-    one = _vec(1)
-    one.fork([77], [0], source=env)
+    run_batch(env, scen["actions"][:2], "hk_step")
+    one = GpuVec(1)
+    one.env.fork([77], [0], source=env.env)
     rng = np.random.default_rng(77)
     for t in range(5):
         a = rng.uniform(-1, 1, (N_ARENAS, 8)).astype(np.float32)
-        g = _np(env.step(_t(a), with_agent_two=True))
-        h = _np(one.step(_t(a[77:78]), with_agent_two=True))
-        for f in FIELDS:
+        g = vars(env.step(a, with_agent_two=True))
+        h = vars(one.step(a[77:78], with_agent_two=True))
+        for f in STEP_FIELDS:
             assert np.array_equal(g[f][77:78].view(np.uint8), h[f].view(np.uint8)), (t, f)
-    assert torch.equal(env.snapshot([77]).blob, one.snapshot().blob)
+    assert torch.equal(env.env.snapshot([77]).blob, one.env.snapshot().blob)
     (s0, x0), (s1, x1) = env.get_state(), one.get_state()
-    assert torch.equal(s0[77:78].view(torch.int32), s1.view(torch.int32)) and torch.equal(x0[77:78], x1)
-    _no_bad_index(env, one)
+    assert np.array_equal(s0[77:78].view(np.uint32), s1.view(np.uint32)) and np.array_equal(x0[77:78], x1)
+    no_bad_index(env, one)
     env.close()
     one.close()
 
@@ -226,15 +148,15 @@ def test_facade_snapshot_restore_around_the_step_server(scen):  # noqa: F811
     assert h.time == 4
     assert cont() == first
     env = _zoo_env(scen)
-    _advance(env, scen["actions"][:2], "step")
-    h.restore(env.snapshot([77]))
+    run_batch(env, scen["actions"][:2], "hk_step")
+    h.restore(env.env.snapshot([77]))
     a = scen["actions"][2]
-    g = _np(env.step(_t(a), with_agent_two=True))
+    g = vars(env.step(a, with_agent_two=True))
     o, r, d, _, info = h.step(a[77])
     assert np.array_equal(o, g["obs"][77].astype(np.float64)) and np.float32(r) == g["reward"][77]
     assert bool(d) == bool(g["done"][77])
     with pytest.raises(ValueError):
-        h.restore(env.snapshot([1, 2]))
+        h.restore(env.env.snapshot([1, 2]))
     h.close()
     env.close()
     # the fused opponent's phase travels with the arena, and its host mirror follows a restore
@@ -269,14 +191,14 @@ def test_copy_between_keep_modes_is_invalid():
         a.fork([0, 1], [1, 2])
     with pytest.raises(ValueError, match="out of range"):
         a.fork([0], [4])
-    _no_bad_index(a, b)
+    no_bad_index(a, b)
     a.close()
     b.close()
 
 
 def test_out_of_range_entries_are_counted_on_the_device(scen):  # noqa: F811
     """With assume_valid the kernel's own check stands: bad entries copy nothing and are counted, exactly."""
-    env = _zoo_env(scen)
+    env = _zoo_env(scen).env
     dst = _vec(130)
     before = dst.snapshot().blob.clone()
     idx = torch.arange(130, device=DEV)
@@ -294,9 +216,9 @@ def test_out_of_range_entries_are_counted_on_the_device(scen):  # noqa: F811
 
 def test_fork_replays_from_a_graph(scen):  # noqa: F811
     """(8) a fork recorded in a torch.cuda.graph (a single branch) and replayed gives the eager call's arenas."""
-    env = _zoo_env(scen)
-    _advance(env, scen["actions"][:2], "step")
-    dst = _vec(128)
+    zoo = _zoo_env(scen)
+    run_batch(zoo, scen["actions"][:2], "hk_step")
+    env, dst = zoo.env, _vec(128)
     g = torch.Generator().manual_seed(3)
     d_idx = torch.randperm(128, generator=g)[:90].to(DEV)
     s_idx = torch.randint(0, N_ARENAS, (90,), generator=g).to(DEV)
@@ -311,7 +233,7 @@ def test_fork_replays_from_a_graph(scen):  # noqa: F811
     dst.reset()
     graph.replay()
     assert torch.equal(dst.snapshot(d_idx).blob, eager)
-    _no_bad_index(env, dst)
+    no_bad_index(env, dst)
     env.close()
     dst.close()
 
@@ -365,6 +287,6 @@ def test_lookahead_against_an_oracle_batch(oracle):
     assert torch.equal(st.view(torch.int32), st_before[0].view(torch.int32)) and torch.equal(aux, st_before[1])
     assert torch.equal(env.snapshot().blob, live_before)
     assert env.counters()[N.CNT_STEPS] == hist * c["n_live"]
-    _no_bad_index(env, la.ws)
+    no_bad_index(env, la.ws)
     la.close()
     env.close()

@@ -29,6 +29,7 @@ import nonfinite_cases as C  # noqa: E402
 import value_ref as V  # noqa: E402
 from hockey_amd import _native as N  # noqa: E402
 from hockey_amd import learner_hip as LH  # noqa: E402
+from scene_lockstep import require_gfx950  # noqa: E402
 from vec_lockstep import FIELDS, first_mismatch  # noqa: E402
 
 DEV = "cuda:0"
@@ -38,8 +39,7 @@ POISON = (float("nan"), float("inf"), float("-inf"), 3e38)
 
 @pytest.fixture(scope="module", autouse=True)
 def _gpu():
-    assert torch.cuda.is_available(), "GPU tests need the MI355X (gfx950)"
-    assert "gfx950" in torch.cuda.get_device_properties(0).gcnArchName
+    require_gfx950()
 
 
 # ---------------------------------------------------------------------------------------------------- step kernel

@@ -13,14 +13,22 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+from functools import partial  # noqa: E402
+
 from hockey_amd import _native as N  # noqa: E402
 from hockey_amd.placement import np_random, placement  # noqa: E402
+from scene_lockstep import GpuVec, batched_lockstep, require_gfx950, world_lockstep  # noqa: E402
+from vec_lockstep import first_mismatch  # noqa: E402
+
+# the two game locksteps of tests/scene_lockstep.py on the GPU (test_hostcheck_parity.py: the same two on the host
+# build); the batched one takes the second half of its steps through hk_rollout and compares the phases too
+_lockstep = partial(world_lockstep, GpuVec)
+_bench_path_lockstep = partial(batched_lockstep, GpuVec)
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _gpu():
-    assert torch.cuda.is_available(), "GPU tests need the MI355X (gfx950)"
-    assert "gfx950" in torch.cuda.get_device_properties(0).gcnArchName
+    require_gfx950()
 
 
 def _vec(n, keep=True, mode=0, **kw):
@@ -95,50 +103,6 @@ def _oracle_worlds(oracle, n, keep, mode, params, max_t):
         w.reset(params[i], max_t)
         ws.append(w)
     return ws
-
-
-def _lockstep(oracle, mode, n, steps, seed, policy_mix=True):
-    """Step GPU and oracle arenas with identical actions; return the first divergence or None."""
-    keep = True
-    env = _vec(n, keep=keep, mode=mode)
-    params = np.zeros((n, 6), np.float32)
-    for i in range(n):
-        rng, _ = np_random(seed * 100_000 + i)
-        params[i], max_t = placement(mode, bool(i % 2), rng)
-    env.reset_params(params)
-    ws = _oracle_worlds(oracle, n, keep, mode, params, max_t)
-    rng = np.random.default_rng(seed)
-    phases = rng.uniform(0, np.pi, (n, 2))
-    obs = np.stack([w.obs() for w in ws]).astype(np.float64)
-    obs2 = np.stack([w.obs_two() for w in ws]).astype(np.float64)
-    n_toi = 0
-    for t in range(steps):
-        acts = rng.uniform(-1, 1, (n, 8)).astype(np.float32)
-        if policy_mix:  # half the arenas play strong-vs-strong BasicOpponent (contacts, shots, goals)
-            for i in range(0, n, 2):
-                a1, phases[i, 0] = oracle.basic_opponent(0, 1, phases[i, 0], 0.1, obs[i])
-                a2, phases[i, 1] = oracle.basic_opponent(0, 1, phases[i, 1], 0.1, obs2[i])
-                acts[i] = np.concatenate([a1, a2]).astype(np.float32)
-        res = env.step(acts, with_agent_two=True)
-        g_obs, g_r, g_d, g_info = _np(res.obs), _np(res.reward), _np(res.done), _np(res.info)
-        g_obs2, g_r2 = _np(res.obs2), _np(res.reward2)
-        for i, w in enumerate(ws):
-            o, r, d, info, _ = w.step(acts[i])
-            n_toi += w.stats()[1]
-            o2 = w.obs_two()
-            i2, r2 = w.info_two()
-            checks = (("obs", np.array_equal(g_obs[i], o)), ("obs2", np.array_equal(g_obs2[i], o2)),
-                      ("reward", g_r[i] == np.float32(r)), ("reward2", g_r2[i] == np.float32(r2)),
-                      ("done", bool(g_d[i]) == d), ("info", np.array_equal(g_info[i], _f32(info))))
-            for name, ok in checks:
-                if not ok:
-                    return {"step": t, "arena": i, "field": name, "gpu_obs": g_obs[i].tolist(), "cpu_obs": o.tolist()}
-            obs[i], obs2[i] = o, o2
-    st, _ = env.get_state()
-    for i, w in enumerate(ws):
-        assert np.array_equal(_np(st)[i], w.get_raw()[0]), i
-    env.close()
-    return {"n_toi": n_toi}
 
 
 @pytest.mark.parametrize("mode,seed", [(0, 1), (0, 2), (1, 3), (2, 4)])
@@ -269,54 +233,6 @@ def test_rollout_equals_repeated_steps(n):
 
 
 # --------------------------------------------------------------------------------------------- batched contract
-from vec_lockstep import first_mismatch  # noqa: E402
-
-_RES_FIELDS = ("obs", "obs2", "reward", "reward2", "done", "info", "info2", "actions", "final_obs")
-
-
-def _res_np(res, t=None):
-    out = {}
-    for f in _RES_FIELDS:
-        v = getattr(res, f)
-        if v is not None:
-            out[f] = _np(v if t is None else v[t])
-    return out
-
-
-def _bench_path_lockstep(oracle, n, steps, mode, policies, seed, offset=0, diag_flags=0, keep_mode=True,
-                         vel_ref=False, external=False):
-    """GPU (hk_step for the first half, hk_rollout for the rest) vs the oracle's batched context.  external:
-    U(-1.2, 1.2) joint actions (clipped in both) for the external players."""
-    env = _vec(n, keep=keep_mode, mode=mode, policies=policies, auto_reset=True, seed=seed, arena_offset=offset,
-               diag_flags=diag_flags, vel_ref_semantics=vel_ref)
-    ov = oracle.OracleVec(n, keep_mode=keep_mode, mode=mode, policies=policies, auto_reset=True, seed=seed,
-                          arena_offset=offset, vel_ref=vel_ref)
-    rng = np.random.default_rng(seed)
-    acts = rng.uniform(-1.2, 1.2, (steps, n, 8)).astype(np.float32) if external else None
-    half = steps // 2
-    for t in range(half):
-        a = None if acts is None else acts[t]
-        got = _res_np(env.step(a, with_agent_two=True, record_actions=True, final_obs=True))
-        bad = first_mismatch(t, got, ov.step(a, with_agent_two=True, final_obs=True))
-        if bad:
-            return bad
-    ro = env.rollout(steps - half, actions=None if acts is None else torch.as_tensor(acts[half:], device="cuda:0"),
-                     with_agent_two=True, record_actions=True, final_obs=True)
-    for t in range(steps - half):
-        a = None if acts is None else acts[half + t]
-        bad = first_mismatch(half + t, _res_np(ro, t), ov.step(a, with_agent_two=True, final_obs=True))
-        if bad:
-            return bad
-    st, aux = env.get_state()
-    ost, oaux = ov.get_state()
-    assert np.array_equal(_np(st), ost) and np.array_equal(_np(aux), oaux)
-    assert np.array_equal(_np(env.opponent_phase()), ov.phase())
-    c, oc = env.counters(), ov.counters()
-    assert np.array_equal(c[:5], oc[:5]), (c[:7], oc[:7])
-    env.close()
-    return {"counters": c}
-
-
 @pytest.mark.parametrize("mode", [0, 1, 2])
 def test_keep_mode_false_with_physics_lockstep_vs_oracle(oracle, mode):
     """Hockey-v0 with keep_mode=False (hockey_env.py:91): player 2's action at index 3 (:663), no hold / shoot
@@ -366,20 +282,19 @@ def test_per_step_opponent_mix_lockstep_vs_oracle(oracle):
     from {external (self-play actions), weak bot, strong bot} through hk_step_io.policy2, each bot with its
     own phase -- bit-exact against the oracle over episodes with auto-reset."""
     n, steps = 256, 400
-    env = _vec(n, mode=0, policies=("external", "external"), auto_reset=True, seed=31)
+    env = GpuVec(n, mode=0, policies=("external", "external"), auto_reset=True, seed=31)
     ov = oracle.OracleVec(n, mode=0, policies=("external", "external"), auto_reset=True, seed=31)
     rng = np.random.default_rng(31)
     for t in range(steps):
         a = rng.uniform(-1, 1, (n, 8)).astype(np.float32)
         p2 = rng.choice(np.array([0, 2, 3], np.uint8), n)
-        got = _res_np(env.step(a, with_agent_two=True, record_actions=True, final_obs=True,
-                               policy2=torch.as_tensor(p2, device="cuda:0")))
+        got = vars(env.step(a, with_agent_two=True, record_actions=True, final_obs=True, policy2=p2))
         want = ov.step(a, with_agent_two=True, final_obs=True, policy2=p2)
         bad = first_mismatch(t, got, want)
         assert bad is None, bad
     st, aux = env.get_state()
     ost, oaux = ov.get_state()
-    assert np.array_equal(st.cpu().numpy(), ost) and np.array_equal(aux.cpu().numpy(), oaux)
+    assert np.array_equal(st, ost) and np.array_equal(aux, oaux)
     assert env.counters()[N.CNT_EPISODES] > 0
     env.close()
 
@@ -396,13 +311,13 @@ def test_autoreset_external_policy_transitions(oracle):
     """auto_reset with an external player: obs after a done step is the NEW episode's first state (so the
     next action is chosen from it), final_obs holds the terminal observation."""
     n, steps = 128, 300
-    env = _vec(n, mode=2, policies=("external", "strong"), auto_reset=True, seed=12)
+    env = GpuVec(n, mode=2, policies=("external", "strong"), auto_reset=True, seed=12)
     ov = oracle.OracleVec(n, mode=2, policies=("external", "strong"), auto_reset=True, seed=12)
     rng = np.random.default_rng(0)
     resets = 0
     for t in range(steps):
         a = rng.uniform(-1, 1, (n, 8)).astype(np.float32)
-        got = _res_np(env.step(a, with_agent_two=True, record_actions=True, final_obs=True))
+        got = vars(env.step(a, with_agent_two=True, record_actions=True, final_obs=True))
         want = ov.step(a, with_agent_two=True, final_obs=True)
         assert first_mismatch(t, got, want) is None
         d = got["done"].astype(bool)

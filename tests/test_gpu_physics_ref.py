@@ -19,42 +19,14 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 from hockey_amd import _native as N  # noqa: E402
+from scene_lockstep import GpuVec, oracle_run, require_gfx950, same_bits  # noqa: E402
 import physics_scenes as SC  # noqa: E402
 import physics_scenes2 as S2  # noqa: E402
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _gpu():
-    assert torch.cuda.is_available(), "GPU tests need the MI355X (gfx950)"
-    assert "gfx950" in torch.cuda.get_device_properties(0).gcnArchName
-
-
-class GpuArenas:
-    """VecHockeyEnv behind the three calls physics_scenes.run makes."""
-
-    def __init__(self, n, keep_mode, **kw):
-        from hockey_amd.vec_env import VecHockeyEnv
-
-        self.env = VecHockeyEnv(n, keep_mode=keep_mode, mode=0, device="cuda:0", policies=("external", "external"),
-                                auto_reset=False, **kw)
-        self.dbg = torch.zeros((n, N.DEBUG_DIM), dtype=torch.float32, device="cuda:0")
-        self.done = []
-
-    def set_state(self, st, aux):
-        self.env.set_state(np.array(st), np.array(aux))  # the batch's arrays are read-only: torch wants its own
-
-    def step_debug(self, actions):
-        r = self.env.step(torch.as_tensor(np.array(actions), device="cuda:0"), debug=self.dbg)
-        self.done.append(r.done.cpu().numpy().copy())
-        return self.dbg.cpu().numpy()
-
-    def get_state(self):
-        st, aux = self.env.get_state()
-        self._aux = aux.cpu().numpy()
-        return st.cpu().numpy()
-
-    def get_aux(self):
-        return self._aux  # of the get_state just made
+    require_gfx950()
 
 
 @pytest.fixture(scope="module")
@@ -65,34 +37,20 @@ def batches():
 @pytest.fixture(scope="module")
 def want(oracle, batches):
     """OracleVec's states after every step of both batches, computed once."""
-    out = {}
-    for keep, b in batches.items():
-        ov = oracle.OracleVec(b.n, keep_mode=keep, policies=("external", "external"), auto_reset=False)
-        ov.set_state(b.state, b.aux)
-        states = []
-        for k in range(SC.K):
-            ov.step(b.actions[k])
-            states.append(ov.get_state()[0])
-        ov.close()
-        out[keep] = np.stack(states)
-        out[keep].setflags(write=False)
-    return out
+    return {keep: oracle_run(oracle, b.state, b.aux, b.actions, keep_mode=keep, every_step_state=True)["states"]
+            for keep, b in batches.items()}
 
 
 def _run(batch, want, full, **kw):
-    g = GpuArenas(batch.n, batch.keep_mode, **kw)
+    g = GpuVec(batch.n, keep_mode=batch.keep_mode, **kw)
     S, D = SC.run(g, batch)
-    counters = np.asarray(g.env.counters())
-    g.env.close()
+    counters = g.counters()
+    g.close()
     m = SC.measure(batch, S, D)
     if full:
         print({k: v for k, v in m.items() if not k.endswith("_log")})
     SC.check(m, full=full)
-    same = (S[1:].view(np.uint32) == want.view(np.uint32)).all(-1)
-    if not same.all():
-        k, i = (int(x[0]) for x in np.nonzero(~same))
-        pytest.fail("step %d, arena %d (family %s): state differs from the oracle's\n%s\n%s" % (
-            k, i, batch.family[i], S[k + 1, i], want[k, i]))
+    same_bits(S[1:], want, "state after", batch.family)
     assert counters[N.CNT_OVERFLOW] == 0
     return counters
 
@@ -126,42 +84,27 @@ def batch2():
 def want2(oracle, batch2):
     """OracleVec's states, aux rows and done flags after every step of the second batch, computed once."""
     b = batch2
-    ov = oracle.OracleVec(b.n, keep_mode=False, policies=("external", "external"), auto_reset=False)
-    ov.set_state(b.state, b.aux)
-    states, auxs, dones = [], [], []
-    for k in range(SC.K):
-        dones.append(ov.step(b.actions[k])["done"])
-        st, aux = ov.get_state()
-        states.append(st)
-        auxs.append(aux)
-    ov.close()
-    out = (np.stack(states), np.stack(auxs), np.stack(dones))
-    for a in out:
-        a.setflags(write=False)
-    return out
+    run = oracle_run(oracle, b.state, b.aux, b.actions, keep_mode=False, every_step_state=True)
+    done = np.stack([s["done"] for s in run["steps"]])
+    done.setflags(write=False)
+    return run["states"], run["auxs"], done
 
 
-def _same_bits(batch, got, want, what):
-    same = (got.view(np.uint32 if got.dtype.itemsize == 4 else got.dtype) == want.view(
-        np.uint32 if want.dtype.itemsize == 4 else want.dtype)).reshape(got.shape[0], got.shape[1], -1).all(-1)
-    if not same.all():
-        k, i = (int(x[0]) for x in np.nonzero(~same))
-        pytest.fail("step %d, arena %d (family %s %s): %s differs from the oracle's\n%s\n%s" % (
-            k, i, batch.family[i], batch.kind[i], what, got[k, i], want[k, i]))
+def _label(batch):
+    return ["family %s %s" % fk for fk in zip(batch.family, batch.kind)]
 
 
 def _run2(batch, want, **kw):
-    g = GpuArenas(batch.n, False, **kw)
-    S, D, A = S2.run(g, batch)
-    counters = np.asarray(g.env.counters())
-    done = np.stack(g.done)
-    g.env.close()
+    g = GpuVec(batch.n, keep_mode=False, **kw)
+    S, D, A, done = S2.run(g, batch)
+    counters = g.counters()
+    g.close()
     m = S2.measure(batch, S, D, A)
     print({k: v for k, v in m.items() if not k.endswith("_log")})
     S2.check(m)
-    _same_bits(batch, S[1:], want[0], "state")
-    _same_bits(batch, A[1:].astype(np.int32), want[1], "aux (has_puck, time, done, winner)")
-    _same_bits(batch, done, want[2], "done")
+    same_bits(S[1:], want[0], "state after", _label(batch))
+    same_bits(A[1:], want[1], "aux (has_puck, time, done, winner) after", _label(batch))
+    same_bits(done, want[2], "done of", _label(batch))
     assert counters[N.CNT_OVERFLOW] == 0
     return counters, S, A, done
 
@@ -187,20 +130,16 @@ def test_second_batch_rollout(batch2, want2):
     per step, so G, H, S and P are held here only THROUGH the final state: it must be the oracle's bit for bit, hence
     the step-by-step run's, whose per-step laws the tests above hold.  The goal law is re-asserted on the rollout's own
     done flags and final winner."""
-    from hockey_amd.vec_env import VecHockeyEnv
-
     b = batch2
-    env = VecHockeyEnv(b.n, keep_mode=False, mode=0, device="cuda:0", policies=("external", "external"),
-                       auto_reset=False)
-    env.set_state(np.array(b.state), np.array(b.aux))
-    r = env.rollout(SC.K, torch.as_tensor(np.array(b.actions), device="cuda:0"))
-    done = r.done.cpu().numpy()
-    st, aux = (t.cpu().numpy() for t in env.get_state())
-    counters = np.asarray(env.counters())
-    env.close()
-    _same_bits(b, done, want2[2], "done")
-    _same_bits(b, st[None], want2[0][-1:], "final state")
-    _same_bits(b, aux[None], want2[1][-1:], "final aux")
+    g = GpuVec(b.n, keep_mode=False)
+    g.set_state(b.state, b.aux)
+    done = np.stack([r["done"] for r in g.rollout(b.actions)])
+    st, aux = g.get_state()
+    counters = g.counters()
+    g.close()
+    same_bits(done, want2[2], "done of", _label(b))
+    same_bits(st[None], want2[0][-1:], "final state, rollout", _label(b))
+    same_bits(aux[None], want2[1][-1:], "final aux, rollout", _label(b))
     assert counters[N.CNT_OVERFLOW] == 0
     # Q from the rollout's flags: done in step j exactly when an earlier step's end state overlapped the sensor
     import physics_ref as P

@@ -13,6 +13,7 @@ import seed_cases as SC  # noqa: E402
 from hockey_amd import _native as N  # noqa: E402
 from hockey_amd.constants import Mode  # noqa: E402
 from hockey_amd.placement import np_random, placement  # noqa: E402
+from scene_lockstep import require_gfx950  # noqa: E402
 
 DEV = "cuda:0"
 MODES = (Mode.NORMAL, Mode.TRAIN_SHOOTING, Mode.TRAIN_DEFENSE)
@@ -21,8 +22,7 @@ N_TWIN = 200  # three full waves and a partial one
 
 @pytest.fixture(scope="module", autouse=True)
 def _gpu():
-    assert torch.cuda.is_available(), "GPU tests need the MI355X (gfx950)"
-    assert "gfx950" in torch.cuda.get_device_properties(0).gcnArchName
+    require_gfx950()
 
 
 def _vec(n, mode=Mode.NORMAL, **kw):

@@ -17,6 +17,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 from hockey_amd import _native as N  # noqa: E402
+from scene_lockstep import GpuVec, oracle_run, require_gfx950, same_bits  # noqa: E402
 import sleep_scenes as ZS  # noqa: E402
 
 BATCHES = {"main": ("main", False), "z1": ("z1", False), "z1_keep": ("z1", True)}
@@ -25,34 +26,7 @@ SNAP_AT = 40
 
 @pytest.fixture(scope="module", autouse=True)
 def _gpu():
-    assert torch.cuda.is_available(), "GPU tests need the MI355X (gfx950)"
-    assert "gfx950" in torch.cuda.get_device_properties(0).gcnArchName
-
-
-def _env(batch, **kw):
-    from hockey_amd.vec_env import VecHockeyEnv
-
-    return VecHockeyEnv(batch.n, keep_mode=batch.keep_mode, mode=0, device="cuda:0",
-                        policies=("external", "external"), auto_reset=False, **kw)
-
-
-class GpuArenas:
-    """VecHockeyEnv behind the three calls sleep_scenes.run makes."""
-
-    def __init__(self, batch, **kw):
-        self.env = _env(batch, **kw)
-        self.dbg = torch.zeros((batch.n, N.DEBUG_DIM), dtype=torch.float32, device="cuda:0")
-
-    def set_state(self, st, aux, mask):
-        c = lambda a: None if a is None else np.array(a)  # noqa: E731  (the batch's arrays are read-only)
-        self.env.set_state(c(st), c(aux), c(mask))
-
-    def step_debug(self, actions):
-        self.env.step(torch.as_tensor(np.array(actions), device="cuda:0"), debug=self.dbg)
-        return self.dbg.cpu().numpy()
-
-    def get_state(self):
-        return self.env.get_state()[0].cpu().numpy()
+    require_gfx950()
 
 
 @pytest.fixture(scope="module")
@@ -66,42 +40,25 @@ def want(oracle, batches):
     every step, and the state before that set_state; computed once."""
     out = {}
     for name, b in batches.items():
-        ov = oracle.OracleVec(b.n, keep_mode=b.keep_mode, policies=("external", "external"), auto_reset=False)
-        ov.set_state(b.state, b.aux)
-        S, obs, before = [np.array(b.state)], [], None
-        for k in range(ZS.K):
-            if k == ZS.T0:
-                before = S[-1]
-                patch = b.twin_patch(S[-1])
-                if patch is not None:
-                    ov.set_state(patch[0], None, patch[1])
-                    S[-1] = ov.get_state()[0]
-            obs.append(ov.step(b.actions[k])["obs"])
-            S.append(ov.get_state()[0])
-        ov.close()
-        out[name] = (np.stack(S), np.stack(obs), before)
+        run = oracle_run(oracle, b.state, b.aux, b.actions, keep_mode=b.keep_mode, every_step_state=True,
+                         patch=lambda k, st, b=b: b.twin_patch(st) if k == ZS.T0 else None)
+        S = np.concatenate([b.state[None], run["states"]])
+        before, S[ZS.T0] = run["patched"].get(ZS.T0, (S[ZS.T0], S[ZS.T0]))
+        out[name] = (S, np.stack([s["obs"] for s in run["steps"]]), before)
         for a in out[name]:
             a.setflags(write=False)
     return out
 
 
-def _same_bits(batch, got, want, what, first=0, ref="the oracle's"):
-    same = (got.view(np.uint32) == want.view(np.uint32)).all(-1)
-    if not same.all():
-        k, i = (int(x[0]) for x in np.nonzero(~same))
-        pytest.fail("%s %d, arena %d (family %s): differs from %s\n%s\n%s" % (
-            what, k + first, i, batch.family[i], ref, got[k, i], want[k, i]))
-
-
 def _run(batch, want, **kw):
-    g = GpuArenas(batch, **kw)
+    g = GpuVec(batch.n, keep_mode=batch.keep_mode, **kw)
     S, D = ZS.run(g, batch)
-    counters = np.asarray(g.env.counters())
-    g.env.close()
+    counters = g.counters()
+    g.close()
     m = ZS.measure(batch, S, D)
     print(m)
     ZS.check(m, batch)
-    _same_bits(batch, S, want[0], "state before step")
+    same_bits(S, want[0], "state before", batch.family)
     assert counters[N.CNT_OVERFLOW] == 0
     return S, counters
 
@@ -141,20 +98,20 @@ def test_main_batch_rollout_in_two_launches(batches, want):
     per-step laws the tests above hold."""
     b = batches["main"]
     S, obs, before = want["main"]
-    env = _env(b)
-    env.set_state(np.array(b.state), np.array(b.aux))
-    acts = torch.as_tensor(np.array(b.actions), device="cuda:0")
-    o1 = env.rollout(ZS.T0, acts[:ZS.T0]).obs.cpu().numpy()
-    mid = env.get_state()[0].cpu().numpy()
+    g = GpuVec(b.n, keep_mode=b.keep_mode)
+    g.set_state(b.state, b.aux)
+    o1 = [r["obs"] for r in g.rollout(b.actions[:ZS.T0])]
+    mid = g.get_state()[0]
     patch = b.twin_patch(mid)
-    env.set_state(patch[0], None, patch[1])
-    mid2 = env.get_state()[0].cpu().numpy()
-    o2 = env.rollout(ZS.K - ZS.T0, acts[ZS.T0:]).obs.cpu().numpy()
-    end = env.get_state()[0].cpu().numpy()
-    counters = np.asarray(env.counters())
-    env.close()
-    _same_bits(b, np.concatenate([o1, o2]), obs, "observation after step")
-    _same_bits(b, np.stack([mid, mid2, end]), np.stack([before, S[ZS.T0], S[-1]]), "state (T0, T0 patched, end)")
+    g.set_state(patch[0], None, patch[1])
+    mid2 = g.get_state()[0]
+    o2 = [r["obs"] for r in g.rollout(b.actions[ZS.T0:])]
+    end = g.get_state()[0]
+    counters = g.counters()
+    g.close()
+    same_bits(np.stack(o1 + o2), obs, "observation after", b.family)
+    same_bits(np.stack([mid, mid2, end]), np.stack([before, S[ZS.T0], S[-1]]), "state (0: T0, 1: T0 patched, 2: end),",
+              b.family)
     assert counters[N.CNT_OVERFLOW] == 0
 
 
@@ -163,15 +120,15 @@ def test_snapshot_with_sleeping_pucks_continues_bit_for_bit(batches, main_run):
     b = batches["main"]
     z1 = b.family == "Z1"
     assert (main_run[SNAP_AT][z1, 15:18] == 0).all() and (main_run[ZS.N_SLEEP - 1][z1, 15:17] != 0).any(-1).all()
-    g = GpuArenas(b)
+    g = GpuVec(b.n, keep_mode=b.keep_mode)
     head, _ = ZS.run(g, b, 0, SNAP_AT)
     snap = g.env.snapshot()
-    g.env.close()
-    h = GpuArenas(b)
+    g.close()
+    h = GpuVec(b.n, keep_mode=b.keep_mode)
     h.env.restore(snap)
     tail, _ = ZS.run(h, b, SNAP_AT, ZS.K)
-    counters = np.asarray(h.env.counters())
-    h.env.close()
-    _same_bits(b, head, main_run[:SNAP_AT + 1], "state before step", 0, "the uninterrupted run's")
-    _same_bits(b, tail, main_run[SNAP_AT:], "state before step", SNAP_AT, "the uninterrupted run's")
+    counters = h.counters()
+    h.close()
+    same_bits(head, main_run[:SNAP_AT + 1], "state before", b.family, 0, "the uninterrupted run's")
+    same_bits(tail, main_run[SNAP_AT:], "state before", b.family, SNAP_AT, "the uninterrupted run's")
     assert counters[N.CNT_OVERFLOW] == 0

@@ -19,16 +19,15 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 from hockey_amd import _native as N  # noqa: E402
+from scene_lockstep import (STEP_FIELDS, GpuVec, check_run, oracle_run, require_gfx950, scene_env,  # noqa: E402
+                            wave_permutation)
 from vec_lockstep import first_mismatch  # noqa: E402
 import wave_zoo as W  # noqa: E402
-
-FIELDS = ("obs", "obs2", "reward", "reward2", "done", "info", "info2")
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _gpu():
-    assert torch.cuda.is_available(), "GPU tests need the MI355X (gfx950)"
-    assert "gfx950" in torch.cuda.get_device_properties(0).gcnArchName
+    require_gfx950()
 
 
 @pytest.fixture(scope="module")
@@ -39,112 +38,48 @@ def batch():
 @pytest.fixture(scope="module")
 def want(oracle, batch):
     """The oracle's answer for the composed batch, computed once: per-step outputs, final state, counters."""
-    ov = oracle.OracleVec(batch.n, policies=("external", "external"), auto_reset=False)
-    ov.set_state(batch.state, batch.aux)
-    steps = [ov.step(batch.actions[t], with_agent_two=True) for t in range(W.K)]
-    out = {"steps": steps, "state": ov.get_state(), "counters": ov.counters()}
-    ov.close()
-    for s in steps:
-        for v in s.values():
-            v.setflags(write=False)
-    return out
+    return oracle_run(oracle, batch.state, batch.aux, batch.actions)
 
 
-def _env(batch, perm=None, **kw):
-    from hockey_amd.vec_env import VecHockeyEnv
-
-    env = VecHockeyEnv(batch.n, keep_mode=True, mode=0, device="cuda:0", policies=("external", "external"),
-                       auto_reset=False, **kw)
-    sel = slice(None) if perm is None else perm
-    env.set_state(batch.state[sel], batch.aux[sel])
-    return env
-
-
-def _np(res, t=None):
-    return {f: (getattr(res, f) if t is None else getattr(res, f)[t]).detach().cpu().numpy() for f in FIELDS}
-
-
-def _check_step(batch, t, got, want_t, how):
-    bad = first_mismatch(t, got, want_t, fields=FIELDS)
-    if bad:
-        ctx = batch.describe(bad["arena"], t) if "arena" in bad else ""
-        pytest.fail("%s: %s\n%s" % (how, bad, ctx))
-
-
-def _check_end(batch, env, want, how, large):
-    st, aux = env.get_state()
-    st, aux = st.cpu().numpy(), aux.cpu().numpy()
-    ost, oaux = want["state"]
-    ok = (st.view(np.uint32) == ost.view(np.uint32)).all(1) & (aux == oaux).all(1)
-    if not ok.all():
-        i = int(np.nonzero(~ok)[0][0])
-        pytest.fail("%s: final state of arena %d differs\n%s" % (how, i, batch.describe(i, W.K - 1)))
-    c = np.asarray(env.counters()).astype(np.int64)
-    assert np.array_equal(c[:5], want["counters"][:5]), (how, c[:8], want["counters"][:5])
-    assert c[N.CNT_TOI] == batch.toi.sum(), how  # the fixture's TOI labels: every TOI row's event counts
-    assert c[N.CNT_OVERFLOW] == 0, how
-    large(int(c[N.CNT_LARGE_ISLANDS]))
-
-
-def _eq(a, b):
-    assert a == b, (a, b)
+def _check(batch, want, path, how, large, **kw):
+    """The batch through `path` against the oracle: outputs, final state, counters, the fixture's TOI labels."""
+    check_run(scene_env(GpuVec, batch.state, batch.aux, **kw), batch.actions, path, want, how,
+              describe=batch.describe, toi=batch.toi, large=large)
 
 
 def test_zoo_hk_step_vs_oracle(batch, want):
     """(i) K hk_step launches.  The large-island counter equals what the fixture's labels predict: lanes with more
     island contacts than register slots, TOI mini-islands with more than two."""
-    env = _env(batch)
-    for t in range(W.K):
-        res = env.step(torch.as_tensor(batch.actions[t], device="cuda:0"), with_agent_two=True)
-        _check_step(batch, t, _np(res), want["steps"][t], "hk_step")
-    _check_end(batch, env, want, "hk_step", lambda c: _eq(c, batch.large))
-    env.close()
+    _check(batch, want, "hk_step", "hk_step", batch.large)
 
 
 def test_zoo_hk_rollout_vs_oracle(batch, want):
     """(ii) a fresh context through one hk_rollout(K): step_kernel<true>, a separate instantiation."""
-    env = _env(batch)
-    ro = env.rollout(W.K, actions=torch.as_tensor(batch.actions, device="cuda:0"), with_agent_two=True)
-    for t in range(W.K):
-        _check_step(batch, t, _np(ro, t), want["steps"][t], "hk_rollout")
-    _check_end(batch, env, want, "hk_rollout", lambda c: _eq(c, batch.large))
-    env.close()
+    _check(batch, want, "hk_rollout", "hk_rollout", batch.large)
 
 
 def test_zoo_large_island_path_vs_oracle(batch, want):
     """(iii) HK_DIAG_LARGE_ISLANDS: every solve of every lane on the HBM slot file."""
-    env = _env(batch, diag_flags=N.DIAG_LARGE_ISLANDS)
-    for t in range(W.K):
-        res = env.step(torch.as_tensor(batch.actions[t], device="cuda:0"), with_agent_two=True)
-        _check_step(batch, t, _np(res), want["steps"][t], "hk_step, large-island path")
-
-    def more(c):
-        assert c > batch.large, (c, batch.large)
-
-    _check_end(batch, env, want, "hk_step, large-island path", more)
-    env.close()
+    _check(batch, want, "hk_step", "hk_step, large-island path", lambda c: c > batch.large,
+           diag_flags=N.DIAG_LARGE_ISLANDS)
 
 
 def test_zoo_lane_permutation_invariance(batch):
     """A lane's result does not depend on its neighbours: with the lanes of every wave permuted (fixed seed), each
     arena's outputs equal those of its unpermuted twin bit for bit.  GPU against GPU, no oracle."""
-    rng = np.random.default_rng(64)
-    perm = np.concatenate([w0 + rng.permutation(min(64, batch.n - w0)) for w0 in range(0, batch.n, 64)])
-    assert np.array_equal(np.sort(perm), np.arange(batch.n)) and (perm // 64 == np.arange(batch.n) // 64).all()
-    a, b = _env(batch), _env(batch, perm=perm)
+    perm = wave_permutation(batch.n)
+    a, b = scene_env(GpuVec, batch.state, batch.aux), scene_env(GpuVec, batch.state[perm], batch.aux[perm])
     for t in range(W.K):
-        ra = _np(a.step(torch.as_tensor(batch.actions[t], device="cuda:0"), with_agent_two=True))
-        rb = _np(b.step(torch.as_tensor(batch.actions[t][perm], device="cuda:0"), with_agent_two=True))
-        twin = {f: ra[f][perm] for f in FIELDS}
-        bad = first_mismatch(t, rb, twin, fields=FIELDS)
+        ra = vars(a.step(batch.actions[t], with_agent_two=True))
+        rb = vars(b.step(batch.actions[t][perm], with_agent_two=True))
+        twin = {f: ra[f][perm] for f in STEP_FIELDS}
+        bad = first_mismatch(t, rb, twin, fields=STEP_FIELDS)
         if bad:
             i = int(perm[bad["arena"]])
             pytest.fail("permuted lane %d (arena %d of the table) differs from its twin: %s\n%s" % (
                 bad["arena"], i, bad, batch.describe(i, t)))
-    sa, xa = a.get_state()
-    sb, xb = b.get_state()
-    p = torch.as_tensor(perm, device="cuda:0")
-    assert torch.equal(sa[p].view(torch.int32), sb.view(torch.int32)) and torch.equal(xa[p], xb)
-    assert np.array_equal(np.asarray(a.counters())[:8], np.asarray(b.counters())[:8])
+    (sa, xa), (sb, xb) = a.get_state(), b.get_state()
+    assert np.array_equal(sa[perm].view(np.uint32), sb.view(np.uint32)) and np.array_equal(xa[perm], xb)
+    assert np.array_equal(a.counters()[:8], b.counters()[:8])
     a.close()
     b.close()

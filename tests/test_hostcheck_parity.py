@@ -5,63 +5,18 @@ This catches logic errors in the device code before a GPU run; the GPU parity te
 then hold the gfx950 binary of the same source to the same oracle.  The harness is test infrastructure
 (never loaded by the product package).
 """
-import os
+from functools import partial
 
 import numpy as np
 import pytest
 
-from hockey_amd.placement import np_random, placement
-
 from hostcheck import HostVec, velocity_diag
+from scene_lockstep import batched_lockstep, world_lockstep
+from vec_lockstep import first_mismatch
 
-
-def _f32(x):
-    return np.asarray(x, np.float64).astype(np.float32)
-
-
-def _lockstep(oracle, mode, n, steps, seed, **env_kw):
-    keep = True
-    env = HostVec(n, keep_mode=keep, mode=mode, **env_kw)
-    params = np.zeros((n, 6), np.float32)
-    for i in range(n):
-        rng, _ = np_random(seed * 100_000 + i)
-        params[i], max_t = placement(mode, bool(i % 2), rng)
-    env.reset_params(params)
-    ws = []
-    for i in range(n):
-        w = oracle.OracleWorld(keep, mode)
-        w.reset(params[i], max_t)
-        ws.append(w)
-    rng = np.random.default_rng(seed)
-    phases = rng.uniform(0, np.pi, (n, 2))
-    obs = np.stack([w.obs() for w in ws]).astype(np.float64)
-    obs2 = np.stack([w.obs_two() for w in ws]).astype(np.float64)
-    n_toi = 0
-    for t in range(steps):
-        acts = rng.uniform(-1, 1, (n, 8)).astype(np.float32)
-        for i in range(0, n, 2):  # half the arenas: strong-vs-strong BasicOpponent (contacts, shots, goals)
-            a1, phases[i, 0] = oracle.basic_opponent(0, 1, phases[i, 0], 0.1, obs[i])
-            a2, phases[i, 1] = oracle.basic_opponent(0, 1, phases[i, 1], 0.1, obs2[i])
-            acts[i] = np.concatenate([a1, a2]).astype(np.float32)
-        res = env.step(acts, with_agent_two=True)
-        for i, w in enumerate(ws):
-            o, r, d, info, _ = w.step(acts[i])
-            n_toi += w.stats()[1]
-            o2 = w.obs_two()
-            i2, r2 = w.info_two()
-            checks = (("obs", np.array_equal(res.obs[i], o)), ("obs2", np.array_equal(res.obs2[i], o2)),
-                      ("reward", res.reward[i] == np.float32(r)), ("reward2", res.reward2[i] == np.float32(r2)),
-                      ("done", bool(res.done[i]) == d), ("info", np.array_equal(res.info[i], _f32(info))))
-            for name, ok in checks:
-                if not ok:
-                    return {"step": t, "arena": i, "field": name}
-            obs[i], obs2[i] = o, o2
-    st, _ = env.get_state()
-    for i, w in enumerate(ws):
-        assert np.array_equal(st[i], w.get_raw()[0]), i
-    out = {"n_toi": n_toi, "counters": env.counters()}
-    env.close()
-    return out
+# the two game locksteps of tests/scene_lockstep.py on the host build (test_gpu_parity.py: the same two on the GPU)
+_lockstep = partial(world_lockstep, HostVec)
+_vec_lockstep = partial(batched_lockstep, HostVec)
 
 
 @pytest.mark.parametrize("mode,seed", [(0, 1), (1, 3), (2, 4)])
@@ -91,35 +46,6 @@ def test_fused_opponents_autoreset_run(oracle):
 
 
 # ------------------------------------------------------------------------------------------------ batched contract
-from vec_lockstep import first_mismatch  # noqa: E402
-
-
-def _vec_lockstep(oracle, n, steps, mode, policies, seed, external=False, offset=0, mix=False, keep_mode=True,
-                  vel_ref=False):
-    """The kernel source (host build) vs the oracle's batched context on the hk_step contract: fused
-    policies with Philox increments (opp_inc NULL), device auto-reset with episode counters.  mix: player 2's
-    policy is drawn per arena and step from {external, weak, strong} (hk_step_io.policy2)."""
-    env = HostVec(n, keep_mode=keep_mode, mode=mode, policies=policies, auto_reset=True, seed=seed,
-                  arena_offset=offset, vel_ref=vel_ref)
-    ov = oracle.OracleVec(n, keep_mode=keep_mode, mode=mode, policies=policies, auto_reset=True, seed=seed,
-                          arena_offset=offset, vel_ref=vel_ref)
-    rng = np.random.default_rng(seed)
-    for t in range(steps):
-        acts = rng.uniform(-1.2, 1.2, (n, 8)).astype(np.float32) if external else None
-        p2 = rng.choice(np.array([0, 2, 3], np.uint8), n) if mix else None
-        got = vars(env.step(acts, with_agent_two=True, record_actions=True, final_obs=True, policy2=p2))
-        want = ov.step(acts, with_agent_two=True, final_obs=True, policy2=p2)
-        bad = first_mismatch(t, got, want)
-        if bad:
-            return bad
-    st, aux = env.get_state()
-    ost, oaux = ov.get_state()
-    assert np.array_equal(st, ost) and np.array_equal(aux, oaux)
-    c, oc = env.counters().astype(np.int64), ov.counters()
-    assert np.array_equal(c[:5], oc[:5]), (c[:7], oc[:7])  # steps, episodes, goals p1 / p2, TOI events
-    return {"counters": c}
-
-
 @pytest.mark.parametrize("mode,steps", [(0, 560), (1, 200), (2, 200)])
 def test_bench_path_vs_oracle_vec(oracle, mode, steps):
     """The benchmarked workload (strong vs strong, in-kernel Philox phase increments, auto-reset with device

@@ -8,49 +8,12 @@ a head-on puck-racket hit; and on a second batch (tests/physics_scenes2.py) to n
 centre of pressure and energy of a racket against a wall, a rink corner and a goal box, to the position solver's closed
 form, and to when a goal is scored.  The oracle's deliberately wrong variants must each fail the law named for it.
 """
-import numpy as np
 import pytest
 
 import physics_scenes as SC
 import physics_scenes2 as S2
 from hostcheck import HostVec
-
-
-class OracleWorlds:
-    """N OracleWorld arenas behind the three calls physics_scenes.run makes."""
-
-    def __init__(self, oracle, n, keep_mode):
-        self.ws = [oracle.OracleWorld(keep_mode, 0) for _ in range(n)]
-
-    def set_state(self, st, aux):
-        for w, s, x in zip(self.ws, st, aux):
-            w.set_raw(s, x)
-
-    def step_debug(self, actions):
-        return np.stack([w.step(a)[4] for w, a in zip(self.ws, actions)])
-
-    def get_state(self):
-        return np.stack([w.get_raw()[0] for w in self.ws])
-
-    def get_aux(self):
-        return np.stack([w.get_raw()[1] for w in self.ws])
-
-
-class HostArenas:
-    def __init__(self, n, keep_mode):
-        self.env = HostVec(n, keep_mode=keep_mode, mode=0, auto_reset=False)
-
-    def set_state(self, st, aux):
-        self.env.set_state(st, aux)
-
-    def step_debug(self, actions):
-        return self.env.step(actions, debug=True).debug
-
-    def get_state(self):
-        return self.env.get_state()[0]
-
-    def get_aux(self):
-        return self.env.get_state()[1]
+from scene_lockstep import OracleWorlds
 
 
 @pytest.fixture(scope="module")
@@ -64,9 +27,10 @@ def batch2():
 
 
 def _measure(oracle, which, batch):
-    env = OracleWorlds(oracle, batch.n, batch.keep_mode) if which == "oracle" else HostArenas(batch.n, batch.keep_mode)
+    env = OracleWorlds(oracle, batch.n, batch.keep_mode) if which == "oracle" else HostVec(batch.n,
+                                                                                         keep_mode=batch.keep_mode)
     if isinstance(batch, S2.Batch2):
-        return S2.measure(batch, *S2.run(env, batch))
+        return S2.measure(batch, *S2.run(env, batch)[:3])
     return SC.measure(batch, *SC.run(env, batch))
 
 

@@ -14,40 +14,9 @@ import pytest
 import sleep_ref as Z
 import sleep_scenes as ZS
 from hostcheck import HostVec
+from scene_lockstep import OracleWorlds, same_bits
 
 WIDE = 1000  # a wrong law misses its tolerance by orders of magnitude, not by rounding
-
-
-class OracleWorlds:
-    """N OracleWorld arenas behind the three calls sleep_scenes.run makes."""
-
-    def __init__(self, oracle, n, keep_mode):
-        self.ws = [oracle.OracleWorld(keep_mode, 0) for _ in range(n)]
-
-    def set_state(self, st, aux, mask):
-        for i, w in enumerate(self.ws):
-            if mask is None or mask[i]:
-                w.set_raw(st[i], w.get_raw()[1] if aux is None else aux[i])
-
-    def step_debug(self, actions):
-        return np.stack([w.step(a)[4] for w, a in zip(self.ws, actions)])
-
-    def get_state(self):
-        return np.stack([w.get_raw()[0] for w in self.ws])
-
-
-class HostArenas:
-    def __init__(self, n, keep_mode):
-        self.env = HostVec(n, keep_mode=keep_mode, mode=0, auto_reset=False)
-
-    def set_state(self, st, aux, mask):
-        self.env.set_state(st, aux, mask)
-
-    def step_debug(self, actions):
-        return self.env.step(actions, debug=True).debug
-
-    def get_state(self):
-        return self.env.get_state()[0]
 
 
 BATCHES = {"main": ("main", False), "z1": ("z1", False), "z1_keep": ("z1", True)}
@@ -64,7 +33,7 @@ def runs(oracle, batches):
     out = {}
     for name, b in batches.items():
         for which in ("oracle", "hostcheck"):
-            env = OracleWorlds(oracle, b.n, b.keep_mode) if which == "oracle" else HostArenas(b.n, b.keep_mode)
+            env = OracleWorlds(oracle, b.n, b.keep_mode) if which == "oracle" else HostVec(b.n, keep_mode=b.keep_mode)
             out[name, which] = ZS.run(env, b)
             for a in out[name, which]:
                 a.setflags(write=False)
@@ -102,12 +71,9 @@ def test_laws_hold(batches, runs, name, which):
 
 
 @pytest.mark.parametrize("name", list(BATCHES))
-def test_oracle_and_kernel_source_agree_bit_for_bit(runs, name):
-    for a, b, what in zip(runs[name, "oracle"], runs[name, "hostcheck"], ("state", "debug row")):
-        same = (a.view(np.uint32) == b.view(np.uint32)).all(-1)
-        if not same.all():
-            k, i = (int(x[0]) for x in np.nonzero(~same))
-            pytest.fail("%s: %s %d, arena %d differs\n%s\n%s" % (name, what, k, i, a[k, i], b[k, i]))
+def test_oracle_and_kernel_source_agree_bit_for_bit(batches, runs, name):
+    for want, got, what in zip(runs[name, "oracle"], runs[name, "hostcheck"], ("state before", "debug row of")):
+        same_bits(got, want, "%s: host build's %s" % (name, what), batches[name].family)
 
 
 # ------------------------------------------------------------------------------------ the wrong variants

@@ -8,15 +8,11 @@ without the lean routine as well (only the counter assertions need it).
 """
 import ctypes
 
-import numpy as np
 import pytest
 
 import toi_lean_zoo as Z
-import wave_zoo as W
 from hostcheck import HostVec, lib
-from vec_lockstep import first_mismatch
-
-FIELDS = ("obs", "obs2", "reward", "reward2", "done", "info", "info2")
+from scene_lockstep import check_run, oracle_run, scene_env
 
 
 def lean_events():
@@ -33,25 +29,11 @@ def batch():
 
 
 def _lockstep(oracle, state, aux, actions, toi, describe):
-    n = state.shape[0]
-    env = HostVec(n)
-    ov = oracle.OracleVec(n, policies=("external", "external"), auto_reset=False)
-    env.set_state(state, aux)
-    ov.set_state(state, aux)
-    for t in range(W.K):
-        got = vars(env.step(actions[t], with_agent_two=True))
-        want = ov.step(actions[t], with_agent_two=True)
-        bad = first_mismatch(t, got, want, fields=FIELDS)
-        assert bad is None, (bad, describe(bad["arena"], t) if "arena" in bad else "")
-    st, ax = env.get_state()
-    ost, oax = ov.get_state()
-    assert np.array_equal(st.view(np.uint32), ost.view(np.uint32)) and np.array_equal(ax, oax)
-    c, oc = env.counters().astype(np.int64), ov.counters()
-    assert np.array_equal(c[:5], oc[:5]) and c[5] == 0
-    assert c[4] == toi.sum()  # the TOI counter against the labels
-    assert c[6] == 0  # no solve on the HBM slot file
-    env.close()
-    ov.close()
+    """W.K steps of the host build against the oracle: outputs, final state, counters 0 to 4, the TOI counter against
+    the labels, no overflow and no solve on the HBM slot file."""
+    want = oracle_run(oracle, state, aux, actions)
+    check_run(scene_env(HostVec, state, aux), actions, "hk_step", want, "host build", describe=describe, toi=toi,
+              large=0)
 
 
 def test_event_waves_host_build_vs_oracle(oracle, batch):

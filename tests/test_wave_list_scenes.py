@@ -1,11 +1,13 @@
 """The work-list overflow batch on the CPU (tests/wave_list_scenes.py): every lane is certain to list the items
 that send its wave round the cooperative drains a second time, and the oracle steps the batch to finite states
-through at least one TOI event.  The waves themselves run only on the GPU (tests/test_gpu_wave_list.py): the host
-build steps one lane at a time."""
+through at least one TOI event, and the kernel source's host build steps it bit for bit like the oracle.  The waves
+themselves run only on the GPU (tests/test_gpu_wave_list.py): the host build steps one lane at a time."""
 import numpy as np
 import pytest
 
 import wave_list_scenes as L
+from hostcheck import HostVec
+from scene_lockstep import check_run, oracle_run, scene_env
 
 
 @pytest.fixture(scope="module")
@@ -46,3 +48,14 @@ def test_oracle_steps_the_batch_to_finite_states_with_toi_events(oracle, batch):
     ov.close()
     assert np.isfinite(st).all()
     assert toi >= 1, toi
+
+
+def test_batch_host_build_vs_oracle(oracle, batch):
+    """The batch through the host build for L.K steps: every step output, the final state and aux rows, counters 0
+    to 4 and no overflow, against the oracle.  Lane by lane: this checks the scenarios, not the waves.  The host
+    build takes the large-island path on some of these lanes, which the oracle does not count, and the scenes carry
+    no TOI labels: neither counter is held here."""
+    want = oracle_run(oracle, batch.state, batch.aux, batch.actions)
+    assert len(want["steps"]) == L.K
+    check_run(scene_env(HostVec, batch.state, batch.aux), batch.actions, "hk_step", want, "host build",
+              describe=batch.describe, toi=None, large=None)

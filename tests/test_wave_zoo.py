@@ -9,7 +9,7 @@ import pytest
 
 import wave_zoo as W
 from hostcheck import HostVec, velocity_diag
-from vec_lockstep import first_mismatch
+from scene_lockstep import check_run, oracle_run, scene_env
 
 
 @pytest.fixture(scope="module")
@@ -131,22 +131,7 @@ def test_predictor_vs_host_build(oracle, zoo):
 def test_composed_batch_host_build_vs_oracle(oracle, batch):
     """(d) The composed batch through the host build is bit-exact to the oracle.  Lane by lane: this checks the
     scenarios (and that the GPU test's reference is the kernel source's own answer), not the mixes."""
-    env = HostVec(batch.n)
-    ov = oracle.OracleVec(batch.n, policies=("external", "external"), auto_reset=False)
-    env.set_state(batch.state, batch.aux)
-    ov.set_state(batch.state, batch.aux)
-    fields = ("obs", "obs2", "reward", "reward2", "done", "info", "info2")
-    for t in range(W.K):
-        got = vars(env.step(batch.actions[t], with_agent_two=True))
-        want = ov.step(batch.actions[t], with_agent_two=True)
-        bad = first_mismatch(t, got, want, fields=fields)
-        assert bad is None, (bad, batch.describe(bad["arena"], t) if "arena" in bad else "")
-        assert not want["done"].any()
-    st, aux = env.get_state()
-    ost, oaux = ov.get_state()
-    assert np.array_equal(st.view(np.uint32), ost.view(np.uint32)) and np.array_equal(aux, oaux)
-    c, oc = env.counters().astype(np.int64), ov.counters()
-    assert np.array_equal(c[:5], oc[:5]) and c[5] == 0
-    assert c[4] == batch.toi.sum()
-    assert c[6] == batch.large
-    env.close()
+    want = oracle_run(oracle, batch.state, batch.aux, batch.actions)
+    assert len(want["steps"]) == W.K and not any(s["done"].any() for s in want["steps"])
+    check_run(scene_env(HostVec, batch.state, batch.aux), batch.actions, "hk_step", want, "host build",
+              describe=batch.describe, toi=batch.toi, large=batch.large)

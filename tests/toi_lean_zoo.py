@@ -16,6 +16,7 @@ The same single scenario is also what the tests run as a one-arena context, wher
 import numpy as np
 
 import wave_zoo as W
+from scene_lockstep import wave_permutation
 
 J = W.J
 SINGLE_LANE = 11
@@ -72,10 +73,7 @@ class LeanBatch:
 
     def permutation(self, seed=64):
         """The lanes of every wave permuted (fixed seed)."""
-        rng = np.random.default_rng(seed)
-        perm = np.concatenate([w0 + rng.permutation(min(64, self.n - w0)) for w0 in range(0, self.n, 64)])
-        assert np.array_equal(np.sort(perm), np.arange(self.n)) and (perm // 64 == np.arange(self.n) // 64).all()
-        return perm
+        return wave_permutation(self.n, seed)
 
     def describe(self, arena, t):
         i = int(self.idx[arena])
